@@ -15,6 +15,11 @@ brackets the timing.  Either an external launcher starts the ranks (torch.distri
 WORLD_SIZE / RANK / LOCAL_RANK), or ``--gpus N`` without WORLD_SIZE makes this process a launcher:
 it starts N rank processes itself (never touching the GPU), prints rank 0's line and fails if any
 rank fails.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the headline line (metric, value,
+unit, ms_per_step, ...).  ``--full`` adds everything else: the untimed passes behind the roofline and
+the work counters, the checks of the timed outputs and the CPU baselines.  ``--dump-outputs DIR``
+writes the arrays the last timed step returned (same arguments: same inputs, run after run).
 """
 
 from __future__ import annotations
@@ -179,6 +184,36 @@ def timed_roofline(kernels: list, K: int, qp_ms_handles: list, ms_per_step: floa
                              "frac": traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}})
     out["frac_kernel"] = out["achieved_kernel"] / FP64_PEAK_TFLOPS
     return out
+
+
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: everything written stays below this
+
+
+def dump_outputs(path: str, groups: list) -> None:
+    """--dump-outputs DIR: what the timed path returned in its last timed step, one DIR/<name>.npy per
+    array.  groups: the output dicts of the handles in batch order (their tensors are joined along the
+    first axis; entries that are not tensors are left out).  float64 stays float64, the small integer
+    types become float32 and every other type float64, so each value is kept exactly.  If the arrays
+    exceed DUMP_MAX_BYTES together, each keeps a fixed sample of its rows (seeded, the same rows for
+    arrays of equal length, in ascending order), so two runs of the same arguments write the same rows."""
+    import torch
+
+    host = {}
+    for name in groups[0]:
+        if not all(torch.is_tensor(g[name]) for g in groups):
+            continue
+        a = torch.cat([g[name].reshape(1) if g[name].dim() == 0 else g[name] for g in groups]).cpu().numpy()
+        small = a.dtype in (np.float32, np.float16, np.int8, np.uint8, np.int16, np.bool_)
+        host[name] = np.ascontiguousarray(a.astype(np.float32 if small else np.float64))
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        for name, a in host.items():
+            keep = max(1, int(a.shape[0] * DUMP_MAX_BYTES / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            host[name] = np.ascontiguousarray(a[rows])
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def seed_range(rank: int, S: int) -> range:
@@ -404,6 +439,7 @@ def bench_admm(args, world: int, rank: int, local: int, dist) -> None:
         with torch.cuda.stream(g["stream"]):
             g["eng"].set_leader_device(g["wins"][t])
             o = g["eng"].step(g["x"], iters, stream=g["stream"], on_solve=on_solve)
+            g["out"] = o
             g["u"].copy_(o["u"][:, 0].view(g["P"], n))
             g["notopt"].add_((o["status"] != 0).sum())
             r = g["env"].step(g["x"], g["u"], g["lead"][t], u_prev=g["u_prev"])
@@ -450,26 +486,10 @@ def bench_admm(args, world: int, rank: int, local: int, dist) -> None:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    for g in groups:
-        notopt.add_(g["notopt"])
-        bad.add_(g["bad"])
-    # QP-launch timing and work counters of one more step (stats synchronise per iteration)
-    acc = {"qp_ms": 0.0, "qps": 0, "it": 0}
-
-    def on_solve(solver):
-        st = solver.stats()
-        acc["qp_ms"] += st.qp_ms
-        acc["qps"] += st.n_candidates
-        acc["it"] += st.qp_iterations
-
-    step(args.warmup + args.steps, on_solve=on_solve)
+    if args.dump_outputs and rank == 0:
+        # the last iteration's local solves of the last timed step, and the states the plant step left
+        dump_outputs(args.dump_outputs, [{**g["out"], "state_next": g["x"]} for g in groups])
     value = S * world * args.steps / dt
-    notional = acc["qps"] * dense_qp_bytes(N) + iters * n * S * instance_io_bytes(N)
-    # per-launch PMC figures of one engine's launches (profile: --streams 1 --platoons S/K); the
-    # event pass above ran the K engines one after the other, so acc["qp_ms"] is their summed time
-    qk = ([("k_l1_root", iters * K), ("k_l1_bound", iters * N * K)] if not quadratic
-          else [("k_bnb_root_coop", iters * K), ("k_bnb_bound_coop", iters * N * K)] if N > 8
-          else [("k_bnb_root", iters * K), ("k_bnb_bound", iters * N * K)])
     result = {
         "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} naive_admm ({iters} ADMM iterations)"
                   + ("" if quadratic else " min_1_norm"),
@@ -483,11 +503,38 @@ def bench_admm(args, world: int, rank: int, local: int, dist) -> None:
                    "cost": "min_2_norm" if quadratic else "min_1_norm",
                    "local_miqps_per_step": iters * n * S * world, "warm_incumbent": N > 8 and not args.no_warm_incumbent,
                    "streams_per_gpu": K, "parallelism": f"seeds-sharded x{world}"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+    for g in groups:
+        notopt.add_(g["notopt"])
+        bad.add_(g["bad"])
+    # QP-launch timing and work counters of one more step (stats synchronise per iteration)
+    acc = {"qp_ms": 0.0, "qps": 0, "it": 0}
+
+    def on_solve(solver):
+        st = solver.stats()
+        acc["qp_ms"] += st.qp_ms
+        acc["qps"] += st.n_candidates
+        acc["it"] += st.qp_iterations
+
+    step(args.warmup + args.steps, on_solve=on_solve)
+    notional = acc["qps"] * dense_qp_bytes(N) + iters * n * S * instance_io_bytes(N)
+    # per-launch PMC figures of one engine's launches (profile: --streams 1 --platoons S/K); the
+    # event pass above ran the K engines one after the other, so acc["qp_ms"] is their summed time
+    qk = ([("k_l1_root", iters * K), ("k_l1_bound", iters * N * K)] if not quadratic
+          else [("k_bnb_root_coop", iters * K), ("k_bnb_bound_coop", iters * N * K)] if N > 8
+          else [("k_bnb_root", iters * K), ("k_bnb_bound", iters * N * K)])
+    result.update({
         "roofline": qp_roofline(acc["qp_ms"], qk, notional, f"admm_n{n}_N{N}" + ("" if quadratic else "_l1")
                                 + f"_P{S // K}"),
         "qps_per_step": acc["qps"], "qp_iters_per_qp": acc["it"] / max(acc["qps"], 1),
         "not_optimal_total": int(notopt.item()), "plant_failures_total": int(bad.item()),
-    }
+    })
     if rank == 0 and not args.no_cpu and args.cpu_budget > 0 and world == 1 and quadratic:
         result["cpu_baseline"] = cpu_baseline_admm(n, N, iters, min(args.cpu_budget, 20.0), cpu_threads())
         result["cpu_baseline_1core"] = cpu_baseline_admm(n, N, iters, min(args.cpu_budget, 20.0) * 0.5, 1)
@@ -671,11 +718,34 @@ def bench_gadmm(args, world: int, rank: int, local: int, dist) -> None:
     if dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    ok = all(bool(torch.isfinite(g["out"]["cost"]).all().item()) for g in groups)
+    ok = args.full and all(bool(torch.isfinite(g["out"]["cost"]).all().item()) for g in groups)
     if dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [g["out"] for g in groups])
+    platoons_total = S * (1 if sharded else world)
+    value = platoons_total * args.steps / dt
+    result = {
+        "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} g_admm ({iters} ADMM iterations)",
+        "value": value, "unit": "platoon-timesteps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "strong" if sharded else "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic: env.reset random-init platoon states (seeded), constant-velocity leader; every timed "
+                "step is a g_admm_control with both warm starts (previous solution from the preceding call)",
+        "config": {"workload": f"fleet_g_admm n={n} N={N} pwa_gear (configs[3])", "n_vehicles": n, "horizon": N,
+                   "admm_iters": iters, "max_rounds": args.max_rounds, "rho": 0.5, "platoons_per_gpu": S,
+                   "streams_per_gpu": K,
+                   "parallelism": (f"vehicles-sharded x{world} (RCCL halo send/recv per ADMM iteration)" if sharded
+                                   else f"seeds-sharded x{world} (replicas, no collective)")},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     # per-launch time of the local-QP kernel: HIP events on the launch stream over one more step
     # (the groups one after the other)
     qp_ev = []
@@ -699,27 +769,14 @@ def bench_gadmm(args, world: int, rank: int, local: int, dist) -> None:
     qp_avg = float(np.mean(qp_ms))
     live_qps = sum(g["eng"].P * g["eng"].m for g in groups) / K  # upper bound: platoons that stopped switching skip their lanes
     notional = live_qps * n_qp_launch * (gadmm_qp_bytes(N) + 8 * (2 + 14 * (N + 1)))
-    platoons_total = S * (1 if sharded else world)
-    value = platoons_total * args.steps / dt
-    result = {
-        "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} g_admm ({iters} ADMM iterations)",
-        "value": value, "unit": "platoon-timesteps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "strong" if sharded else "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic: env.reset random-init platoon states (seeded), constant-velocity leader; every timed "
-                "step is a g_admm_control with both warm starts (previous solution from the preceding call)",
-        "config": {"workload": f"fleet_g_admm n={n} N={N} pwa_gear (configs[3])", "n_vehicles": n, "horizon": N,
-                   "admm_iters": iters, "max_rounds": args.max_rounds, "rho": 0.5, "platoons_per_gpu": S,
-                   "streams_per_gpu": K,
-                   "parallelism": (f"vehicles-sharded x{world} (RCCL halo send/recv per ADMM iteration)" if sharded
-                                   else f"seeds-sharded x{world} (replicas, no collective)")},
+    result.update({
         # the engines' QP launches timed one engine after the other (HIP events on the launch
         # stream); per-launch PMC figures of one engine (profile: --streams 1 --platoons S/K)
         "roofline": qp_roofline(qp_avg * n_qp_launch, [("k_gadmm_qp_coop" if N > 8 else "k_gadmm_qp", n_qp_launch)],
                                 notional, f"gadmm_n{n}_N{N}_P{S // K}"),
         "admm_rounds_per_step": rounds / args.steps, "qp_launches_per_step": launches / args.steps,
         "all_feasible": ok,
-    }
+    })
     if ex is not None:
         result["halo_bytes_per_exchange"] = ex.bytes_per_call
     if rank == 0 and not args.no_cpu and args.cpu_budget > 0 and world == 1:
@@ -832,7 +889,8 @@ def bench_closed_loop(args, world: int, rank: int, local: int, dist) -> None:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    s = solver.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [{**out, "state_next": x}])
     value = S * world * args.steps / dt
     result = {
         "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} decent_mld closed loop",
@@ -844,10 +902,14 @@ def bench_closed_loop(args, world: int, rank: int, local: int, dist) -> None:
         "config": {"workload": f"fleet_decent_mld n={n} N={N} pwa_gear closed loop (observe_states + local MIQPs + "
                                "PlatoonEnv.step on the device)", "n_vehicles": n, "horizon": N,
                    "platoons_per_gpu": S, "parallelism": f"seeds-sharded x{world}"},
-        "qp_kernel_ms_last_step": s.qp_ms, "solve_ms_last_step": s.last_ms,
-        "not_optimal_total": int(notopt.item()), "plant_failures_total": int(bad.sum().item()),
-        "violation_steps_total": int((viol // 100).sum().item()),
     }
+    if args.full:
+        s = solver.stats()
+        result.update({
+            "qp_kernel_ms_last_step": s.qp_ms, "solve_ms_last_step": s.last_ms,
+            "not_optimal_total": int(notopt.item()), "plant_failures_total": int(bad.sum().item()),
+            "violation_steps_total": int((viol // 100).sum().item()),
+        })
     if rank == 0:
         print(json.dumps(result), flush=True)
     if dist:
@@ -933,13 +995,32 @@ def bench_cent(args, world: int, rank: int, local: int, dist) -> None:
     if dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    status = np.concatenate([g[4]["status"].cpu().numpy() for g in groups])
-    nodes = np.concatenate([g[4]["nodes"].cpu().numpy() for g in groups])
-    iters = np.concatenate([g[4]["iters"].cpu().numpy() for g in groups])
     if dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [g[4] for g in groups])
+    value = S * world * args.steps / dt
+    result = {
+        "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} cent_mld (QP cap {args.max_nodes} per platoon)",
+        "value": value, "unit": "platoon-timesteps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic: env.reset random-init platoon states (seeded), constant-velocity leader",
+        "config": {"workload": f"fleet_cent_mld n={n} N={N} pwa_gear (MpcMldCent)", "n_vehicles": n, "horizon": N,
+                   "platoons_per_gpu": S, "max_nodes": args.max_nodes, "streams_per_gpu": K,
+                   "parallelism": f"seeds-sharded x{world}"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+    status = np.concatenate([g[4]["status"].cpu().numpy() for g in groups])
+    nodes = np.concatenate([g[4]["nodes"].cpu().numpy() for g in groups])
+    iters = np.concatenate([g[4]["iters"].cpu().numpy() for g in groups])
     # kernel time: HIP events the library records around the search kernels on the solve stream
     # (K streams: their searches overlap, so the step's wall time)
     # kernel time of the roofline: one more step as ONE handle over all S platoons (the launch size
@@ -958,17 +1039,8 @@ def bench_cent(args, world: int, rank: int, local: int, dist) -> None:
     qps = int(nodes.sum())
     notional = qps * cent_qp_bytes(n, N) + S * 8 * (2 * n + 2 * (N + 1) + n * (3 * N + 2) + 1)
     n_opt = int((status == 0).sum())
-    value = S * world * args.steps / dt
     q = np.percentile(nodes, [50, 90, 99, 100])
-    result = {
-        "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} cent_mld (QP cap {args.max_nodes} per platoon)",
-        "value": value, "unit": "platoon-timesteps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic: env.reset random-init platoon states (seeded), constant-velocity leader",
-        "config": {"workload": f"fleet_cent_mld n={n} N={N} pwa_gear (MpcMldCent)", "n_vehicles": n, "horizon": N,
-                   "platoons_per_gpu": S, "max_nodes": args.max_nodes, "streams_per_gpu": K,
-                   "parallelism": f"seeds-sharded x{world}"},
+    result.update({
         "value_optimal_only": n_opt * world * args.steps / dt,
         "roofline": qp_roofline(kernel_ms, cent_kernels(f"cent_n{n}_N{N}_P{S}"), notional, f"cent_n{n}_N{N}_P{S}"),
         "qps_per_step": qps, "qp_iters_per_qp": float(iters.sum()) / max(qps, 1),
@@ -977,7 +1049,7 @@ def bench_cent(args, world: int, rank: int, local: int, dist) -> None:
         "heaviest": [[int(seeds[j]), int(nodes[j]), int(status[j])] for j in np.argsort(-nodes, kind="stable")[:8]],
         "status_counts": {"optimal": int((status == 0).sum()), "infeasible": int((status == 1).sum()),
                           "node_limit": int((status == 2).sum()), "overflow": int((status == 3).sum())},
-    }
+    })
     if rank == 0 and not args.no_cpu and args.cpu_budget > 0 and world == 1:
         result["cpu_baseline"] = cpu_baseline_cent(n, N, min(args.cpu_budget, 30.0), qps / S, cpu_threads())
         result["cpu_baseline_1core"] = cpu_baseline_cent(n, N, min(args.cpu_budget, 30.0) * 0.5, qps / S, 1)
@@ -1043,8 +1115,17 @@ def main() -> None:
     ap.add_argument("--platoons", type=int, default=16384, help="platoons per GPU per step")
     ap.add_argument("--n", type=int, default=10)
     ap.add_argument("--N", type=int, default=5)
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-oracle baseline (0 = skip)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the untimed passes that "
+                         "time the QP launches and read the work counters, the roofline from profiles/, the checks "
+                         "of the timed outputs and the CPU baselines (a plain run prints the headline fields only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the arrays the timed path returned in its last step to "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded sample of rows beyond "
+                         "that); several ranks: rank 0's")
+    ap.add_argument("--cpu-budget", type=float, default=15.0,
+                    help="--full: seconds of CPU-oracle baseline (0 = skip)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: no CPU baselines")
     ap.add_argument("--method", choices=["auto", "enum", "bnb"], default="auto",
                     help="region-sequence search (include/hvp.h HVP_METHOD_*)")
     ap.add_argument("--controller", choices=["decent", "admm", "gadmm", "cent"], default="decent",
@@ -1068,7 +1149,7 @@ def main() -> None:
                     help="decent: min_2_norm (default) or min_1_norm (the MILP variant; --method auto = branch and "
                          "bound, enum = exhaustive enumeration up to N = 8)")
     ap.add_argument("--no-roofline-pass", action="store_true",
-                    help="decent: skip the untimed one-handle pass that times the QP launches for the roofline "
+                    help="--full, decent: skip the untimed one-handle pass that times the QP launches for the roofline "
                          "(profile runs of the multi-stream configuration, so the trace holds its launches only)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: start the ranks (gloo), shard the seeds, run the timing protocol around an "
@@ -1174,14 +1255,50 @@ def main() -> None:
     if dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    ok = all(bool((c[4]["status"] == 0).all().item()) for c in chunks)  # the timed steps' own results
-    # the QP launches of the LAST timed step as they ran in the timed configuration (K handles on K
-    # streams, overlapping): each handle's HIP events around its launches (read after the region)
-    timed_qp_ms = [float(c[0].stats().qp_ms) for c in chunks]
     if dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [c[4] for c in chunks])
+
+    steps_total = S * world * args.steps
+    value = steps_total / dt
+    bnb = method != 1
+    result = {
+        "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} decent_mld" + ("" if quadratic else " min_1_norm"),
+        "value": value,
+        "unit": "platoon-timesteps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic: env.reset random-init platoon states (seeded), constant-velocity neighbour "
+                "predictions, constant-velocity leader",
+        "config": {"workload": (f"fleet_decent_mld n={n} N={N} pwa_gear"
+                                + (" (configs[1])" if (n, N) == (10, 5) else " (configs[4] sweep point)")),
+                   "n_vehicles": n, "horizon": N, "search": "branch-and-bound" if bnb else "enumeration",
+                   "cost": "min_2_norm (MIQP)" if quadratic else "min_1_norm (MILP)",
+                   "platoons_per_gpu": S, "local_miqps_per_step": B * world, "streams_per_gpu": K,
+                   "parallelism": f"seeds-sharded x{world}"},
+    }
+    if not args.full:
+        # a plain run ends here: the headline alone (--full adds the roofline pass, the work counters,
+        # the optimality check of the timed outputs and the CPU baselines)
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    ok = all(bool((c[4]["status"] == 0).all().item()) for c in chunks)  # the timed steps' own results
+    # the QP launches of the LAST timed step as they ran in the timed configuration (K handles on K
+    # streams, overlapping): each handle's HIP events around its launches (read after the region)
+    timed_qp_ms = [float(c[0].stats().qp_ms) for c in chunks]
 
     # per-launch kernel time (HIP events recorded by the library on the solve stream around the
     # QP launches) and work counters: a second pass of the same steps, outside the timed region
@@ -1215,9 +1332,6 @@ def main() -> None:
         fallback += s.n_fallback
     del ev
 
-    steps_total = S * world * args.steps
-    value = steps_total / dt
-    bnb = method != 1
     # QP time per step: the root kernel + the N bound launches (B&B) or K_qp_gi (enumeration),
     # each bracketed by HIP events the library records on the solve stream
     qp_step_ms = float(np.mean(qp_ms))
@@ -1265,32 +1379,13 @@ def main() -> None:
                                            f"decent_n{n}_N{N}" + ("" if bnb else "_enum") + ("" if quadratic else "_l1")
                                            + f"_P{S}_s{K}")
 
-    result = {
-        "metric": f"MPC timesteps/sec (whole platoon) at n={n} N={N} decent_mld" + ("" if quadratic else " min_1_norm"),
-        "value": value,
-        "unit": "platoon-timesteps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic: env.reset random-init platoon states (seeded), constant-velocity neighbour "
-                "predictions, constant-velocity leader",
-        "config": {"workload": (f"fleet_decent_mld n={n} N={N} pwa_gear"
-                                + (" (configs[1])" if (n, N) == (10, 5) else " (configs[4] sweep point)")),
-                   "n_vehicles": n, "horizon": N, "search": "branch-and-bound" if bnb else "enumeration",
-                   "cost": "min_2_norm (MIQP)" if quadratic else "min_1_norm (MILP)",
-                   "platoons_per_gpu": S, "local_miqps_per_step": B * world, "streams_per_gpu": K,
-                   "parallelism": f"seeds-sharded x{world}"},
+    result.update({
         "roofline": roofline,
         "qps_per_step": cand_per_step,
         "qp_iters_per_candidate": iters / max(cand, 1),
         "ipm_fallbacks_per_step": fallback / args.steps,
         "all_optimal": ok,
-    }
+    })
     if rank == 0 and not args.no_cpu and args.cpu_budget > 0 and world == 1:
         # every core this job may use: the pool gives each GPU a 16-core share (OMP_NUM_THREADS=16
         # on the box; nproc shows the whole machine), plus a 1-core run
