@@ -140,6 +140,12 @@ EXPORTS = {
     "hvp_abi_sizes": ([_I32P], ctypes.c_int),
 }
 
+# the extension header include/hvp_seq.h (sequential MLD controller): an addition to ABI 5 with its
+# own table, so EXPORTS stays the mirror of include/hvp.h
+EXPORTS_SEQ = {
+    "hvp_seq_stage_params": ([_P] + [ctypes.c_int] * 3 + [_P] * 3 + [ctypes.c_int] * 3 + [_P] * 3, ctypes.c_int),
+}
+
 
 class HvpError(RuntimeError):
     pass
@@ -169,7 +175,7 @@ def load():
         )
     _init_torch_runtime()
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (argt, rest) in EXPORTS.items():
+    for name, (argt, rest) in {**EXPORTS, **EXPORTS_SEQ}.items():
         fn = getattr(lib, name)
         fn.argtypes = argt
         fn.restype = rest

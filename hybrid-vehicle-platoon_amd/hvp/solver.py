@@ -208,6 +208,41 @@ class BatchSolver:
         _abi.check(rc, "hvp_decent_params_batch")
         return params, roles
 
+    def seq_stage_params_device(self, i: int, x, xpred, leader_window, leader_index: int = 0,
+                                real_vehicle_as_reference: bool = False, first: bool = False,
+                                params=None, roles=None, stream=None):
+        """hvp_seq_stage_params (include/hvp_seq.h): the parameter blocks and roles of stage vehicle
+        i of the sequential controller for P platoons (fleet_seq_mld.py:332-386), from the states
+        x (P, 2n), the vehicle-major prediction store xpred (n, P, 2, N+1) and leader_window
+        (P, 2, N+1).  first: no prediction yet (the first step of an episode).  Returns
+        (params (P, stride), roles (P,)), the instances of batch positions 0..P-1."""
+        import torch
+
+        P, n2 = int(x.shape[0]), int(x.shape[1])
+        n = n2 // 2
+        dev = x.device
+        for name, t, shape in (("x", x, (P, n2)), ("xpred", xpred, (n, P, 2, self.N + 1)),
+                               ("leader_window", leader_window, (P, 2, self.N + 1))):
+            if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be a contiguous CUDA float64 {shape} tensor")
+        if params is None:
+            params = torch.empty((P, self.params_stride), dtype=torch.float64, device=dev)
+        if roles is None:
+            roles = torch.empty(P, dtype=torch.int32, device=dev)
+        for name, t, dt, size in (("params", params, torch.float64, P * self.params_stride),
+                                  ("roles", roles, torch.int32, P)):
+            if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != size:
+                raise ValueError(f"{name} must be a contiguous CUDA tensor of dtype {dt} with {size} elements")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        rc = self._lib.hvp_seq_stage_params(self._h, P, n, int(i), ptr(x), ptr(xpred), ptr(leader_window),
+                                            int(leader_index), 1 if real_vehicle_as_reference else 0,
+                                            1 if first else 0, ptr(params), ptr(roles),
+                                            ctypes.c_void_p(stream.cuda_stream))
+        _abi.check(rc, "hvp_seq_stage_params")
+        return params, roles
+
     # -------------------------------------------------------------- fixed-control evaluation
     def evaluate_device(self, sys_idx, roles, params, gears, u, stream=None) -> dict:
         """Cost of fixed controls u (B, N) and gear labels (B, N) on the device (hvp_evaluate_batch:
