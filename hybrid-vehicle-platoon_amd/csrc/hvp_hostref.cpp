@@ -516,6 +516,26 @@ void solve_one_bnb(const hvp_system& S, const hvp::Consts& C, int role, const do
             }
             if (k == N && good) inc = fmin(inc, lb);
         }
+        if (C.l1 && !(g_l1_solver == 1 && N <= HVP_MAX_N_ENUM)) {
+            // second pass over the level (the device's k_l1_retry): every LP the interior point left
+            // unresolved (it stalls at some degenerate optima: the gap collapses while the dual
+            // residual stays) goes to the simplex; only a vertex it certifies optimal resolves the
+            // node -- anything else leaves it as it was
+            for (Node& c : nxt) {
+                if (c.stat != HVP_MAXITER) continue;
+                hvp::LpData<N> D;
+                double yl[N];
+                int it = 0;
+                const int st = hvp::lp_solve_l1<N>(D, S, C, role, prm, c.code, k, c.lo, c.hi, C.max_iter, yl, it);
+                ++nq;
+                nit += it;
+                if (st != hvp::L1_OK) continue;
+                c.stat = 0;
+                c.lb = hvp::l1_direct_cost<N>(yl, S, C, role, prm, c.code, k, c.lo, c.hi);
+                for (int i = 0; i < N; ++i) c.y[i] = yl[i];
+                if (k == N) inc = fmin(inc, c.lb);
+            }
+        }
         lvl.swap(nxt);
     }
     *nodes = nq;
@@ -580,11 +600,14 @@ void solve_one_bnb(const hvp_system& S, const hvp::Consts& C, int role, const do
 }
 
 template <int N>
-void solve_range(const hvp_problem& P, const hvp_system* systems, int B, const int32_t* sys, const int32_t* role,
+int solve_range(const hvp_problem& P, const hvp_system* systems, int B, const int32_t* sys, const int32_t* role,
                  const double* params, double* u, double* x, int8_t* region, double* cost, int32_t* status,
                  int32_t* nodes, int32_t* iters, int nthreads, double* xf = nullptr, double* xb = nullptr) {
     const hvp::Consts C = make_consts(P);
     const int stride = C.stride;
+    // the naive-ADMM min_1_norm local problem (copies as LP variables, hvp_lane.h l1_admm_node_lp) has
+    // no host build: the decentralised LP below would read its params row in the wrong layout
+    if (C.form == HVP_FORM_ADMM && C.l1) return HVP_E_UNSUPPORTED;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
     for (int i = 0; i < B; ++i) {
         const bool bnb = P.method == HVP_METHOD_BNB ||
@@ -601,6 +624,7 @@ void solve_range(const hvp_problem& P, const hvp_system* systems, int B, const i
                      x + (size_t)i * 2 * (N + 1), region + (size_t)i * N, cost + i, status + i, nodes + i, iters + i,
                      nullptr, nullptr, 0);
     }
+    return 0;
 }
 
 // switching-ADMM local QP of one vehicle for its sequence (the lane path of k_gadmm_qp)
@@ -739,7 +763,7 @@ int hvp_hostref_solve_batch(const hvp_problem* P, const hvp_system* systems, int
                             double* cost, int32_t* status, int32_t* nodes, int32_t* iters, int nthreads) {
     switch (P->N) {
 #define HVP_CASE(n) \
-    case n: solve_range<n>(*P, systems, B, sys, role, params, u, x, region, cost, status, nodes, iters, nthreads); return 0;
+    case n: return solve_range<n>(*P, systems, B, sys, role, params, u, x, region, cost, status, nodes, iters, nthreads);
         HVP_CASE(2) HVP_CASE(3) HVP_CASE(4) HVP_CASE(5) HVP_CASE(6) HVP_CASE(7) HVP_CASE(8)
         HVP_CASE(9) HVP_CASE(10) HVP_CASE(11) HVP_CASE(12) HVP_CASE(13) HVP_CASE(14) HVP_CASE(15) HVP_CASE(16)
 #undef HVP_CASE
@@ -753,9 +777,10 @@ int hvp_hostref_solve_admm_batch(const hvp_problem* P, const hvp_system* systems
                                  double* cost, int32_t* status, int32_t* nodes, int32_t* iters, double* xf,
                                  double* xb, int nthreads) {
     if (P->formulation != HVP_FORM_ADMM) return HVP_E_ARG;
+    if (!P->quadratic_cost) return HVP_E_UNSUPPORTED;  // min_1_norm copies: the device only (solve_range)
     switch (P->N) {
 #define HVP_CASE(n) \
-    case n: solve_range<n>(*P, systems, B, sys, role, params, u, x, region, cost, status, nodes, iters, nthreads, xf, xb); return 0;
+    case n: return solve_range<n>(*P, systems, B, sys, role, params, u, x, region, cost, status, nodes, iters, nthreads, xf, xb);
         HVP_CASE(2) HVP_CASE(3) HVP_CASE(4) HVP_CASE(5) HVP_CASE(6) HVP_CASE(7) HVP_CASE(8)
         HVP_CASE(9) HVP_CASE(10) HVP_CASE(11) HVP_CASE(12) HVP_CASE(13) HVP_CASE(14) HVP_CASE(15) HVP_CASE(16)
 #undef HVP_CASE

@@ -1038,7 +1038,7 @@ struct L1AdmmWave {
 // Mehrotra predictor-corrector of l1_wave_solve with the copy groups (L1AdmmWave).
 template <int N>
 __device__ int l1_admm_wave_solve(L1AdmmWave<N>& A, double* y, double v0, int mh, int mp, int mg, int max_iter,
-                                  int& iters, double* red, int lane, double ylo, double yhi) {
+                                  int& iters, double* red, int lane, double ylo, double yhi, bool leaf) {
     constexpr int NPS = L1Wave<N>::NPS, NHS = L1Wave<N>::NHS, NQ = L1AdmmWave<N>::NQ;
     L1Wave<N>& W = A.W;
     const int mtot = mh + 2 * mp + 2 * mg;
@@ -1100,8 +1100,11 @@ __device__ int l1_admm_wave_solve(L1AdmmWave<N>& A, double* y, double v0, int mh
         // for 100 iterations: admm_l1_local_ct_N5 instance 5, profiles/r06r.log) while y, the copies
         // and the objective stay put.  The iterate with the smallest dual residual among those within
         // a looser test is kept and returned when the strict test is never met (the copies are
-        // re-priced exactly from y, copy_exact).
-        const bool loose = rpm <= 1e-9 && rdm <= 1e-8 * wmx && gap <= 1e-10 * fmax(1.0, fabs(obj));
+        // re-priced exactly from y, copy_exact).  Only at a leaf (K = N), where the price of a feasible
+        // point is what the search compares: at an interior node the price is used as a lower bound,
+        // which a primal point short of the strict test (dual residual up to 1e-8 wmx) does not give
+        // -- such a node stays unresolved (L1_FAIL: it prunes nothing).
+        const bool loose = leaf && rpm <= 1e-9 && rdm <= 1e-8 * wmx && gap <= 1e-10 * fmax(1.0, fabs(obj));
         if (loose && rdm < best_rdm) {
             best_rdm = rdm;
 #pragma unroll
@@ -1212,7 +1215,8 @@ __device__ int l1_admm_node_lp(const hvp_system& S, const hvp::Consts& C, int rl
     L1AdmmWave<N> A;
     int mh = 0, mp = 0, mg = 0;
     A.load(S, C, rl, prm, code, K, rlo, rhi, lane, mh, mp, mg, red + kL1Lds<N>);
-    const int st = l1_admm_wave_solve<N>(A, y, prm[1], mh, mp, mg, C.max_iter, iters, red, lane, S.vmin, S.vmax);
+    const int st = l1_admm_wave_solve<N>(A, y, prm[1], mh, mp, mg, C.max_iter, iters, red, lane, S.vmin, S.vmax,
+                                            K == N);
     cost = 0.0;
     if (st == hvp::L1_OK) {
         const double own = hvp::l1_direct_cost<N>(y, S, C, rl & HVP_ROLE_TRACK_LEADER, prm, code, K, rlo, rhi, 8);
@@ -2229,6 +2233,57 @@ __global__ __launch_bounds__((kL1BlockOfA<N, ADMM>)) __attribute__((amdgpu_waves
         }
     }
     if (lane == 0 && iter_sum) atomicAdd(&ws.counter[1], iter_sum);
+}
+
+// Second pass over level k of the decentralised min_1_norm search after k_l1_bound: the LPs the
+// wave interior point left unresolved (L1_FAIL: at some degenerate optima -- active w = 1e4 safe
+// hinges, a slow front and a fast back vehicle -- its complementarity gap collapses while the dual
+// residual stays above the stop test, whatever the iteration cap) go to the per-lane simplex of
+// hvp_lp.h, one LP per lane, the step data in the lane's own array.  They are rare (about one
+// instance in 2,500 at n = 10, N = 10 holds any), so the kernel normally reads the level's
+// statuses and ends; the wave kernels' registers and LDS are untouched.  Only a vertex the simplex
+// certifies optimal resolves the node; anything else leaves it as k_l1_bound wrote it (an interior
+// node prunes nothing, a leaf in contention makes the instance HVP_MAXITER).  Every unresolved LP
+// of the level is tried, whatever the incumbent, so the LP counts do not depend on the scheduling.
+// The host build runs the same pass (hvp_hostref.cpp solve_one_bnb).
+constexpr int kL1RetryBlock = 64;
+template <int N>
+__global__ __launch_bounds__(kL1RetryBlock) void k_l1_retry(int k, const hvp_system* __restrict__ systems,
+                                                            const int32_t* __restrict__ sys,
+                                                            const int32_t* __restrict__ role,
+                                                            const double* __restrict__ params, hvp::Consts C,
+                                                            Workspace ws) {
+    const int dst = k & 1;
+    const unsigned long long nn = ws.lvl[k];
+    const long long total = (long long)(nn < (unsigned long long)ws.cap ? nn : ws.cap);
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (long long)gridDim.x * blockDim.x) {
+        const int inst = ws.nd_inst[dst][t];
+        if (inst < 0) continue;
+        // k_l1_bound's marks of an unresolved LP (a solved node's bound is a finite cost)
+        if (k < N ? ws.nd_lb[dst][t] != -1e300 : ws.leaf_stat[t] != HVP_MAXITER) continue;
+        const hvp_system& S = systems[sys[inst]];
+        const double* prm = params + (size_t)inst * C.stride;
+        const uint64_t code = ws.nd_code[dst][t];
+        const double rlo = ws.nd_lo[dst][t], rhi = ws.nd_hi[dst][t];
+        hvp::LpData<N> D;
+        double y[N];
+        int it = 0;
+        const int st = hvp::lp_solve_l1<N>(D, S, C, role[inst], prm, code, k, rlo, rhi, C.max_iter, y, it);
+        atomicAdd(&ws.nodes[inst], 1);
+        atomicAdd(&ws.iters[inst], it);
+        atomicAdd(&ws.counter[3], 1ull);
+        atomicAdd(&ws.counter[1], (unsigned long long)it);
+        if (st != hvp::L1_OK) continue;
+        const double c = hvp::l1_direct_cost<N>(y, S, C, role[inst], prm, code, k, rlo, rhi);
+        ws.nd_lb[dst][t] = c;
+        if (k == N) {
+            ws.leaf_stat[t] = 0;
+#pragma unroll
+            for (int j = 0; j < N; ++j) ws.task_y[t * N + j] = y[j];
+            atomicMin(&ws.inc[inst], cost_key(c));
+        }
+    }
 }
 
 // The optimal copies (mpc.x_front.X / x_back.X, fleet_naive_admm.py:413-446) of the naive-ADMM
@@ -4039,9 +4094,14 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
             if (l1_admm)
                 hipLaunchKernelGGL((k_l1_bound<N, true>), dim3(g_l1 * kL1BlockOf<N> / kL1BlockOfA<N, true>), dim3(kL1BlockOfA<N, true>), 0, st, k, h->d_sys, sys, role,
                                    params, h->C, ws);
-            else
+            else {
                 hipLaunchKernelGGL((k_l1_bound<N, false>), dim3(g_l1), dim3(kL1BlockOf<N>), 0, st, k, h->d_sys, sys, role,
                                    params, h->C, ws);
+                HIP_TRY(hipGetLastError());
+                // the level's LPs the interior point left unresolved, by the simplex (normally none)
+                hipLaunchKernelGGL(k_l1_retry<N>, dim3(std::max(1, h->n_cu)), dim3(kL1RetryBlock), 0, st, k, h->d_sys,
+                                   sys, role, params, h->C, ws);
+            }
         } else if constexpr (kCoop<N>) {
             if (ws.norder) {
                 // its counters live in rows 2M and 5M of ws.lvl, bucket 1's count row (hvp_internal.h)

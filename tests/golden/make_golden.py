@@ -50,8 +50,13 @@ Files (numpy .npz, no pickles):
   admm_l1_*.npz       naive ADMM with min_1_norm (LocalMpcADMM(quadratic_cost=False)): local problems
                       (incl. ConstantTime spacing), 3 closed-loop steps at n = 4, N = 5, and configs[2]'s
                       size (n = 10, N = 10, 20 iterations, 2 steps; "admm_l1 n10")
+  l1stall_n10_N10.npz the four n = 10, N = 10 min_1_norm platoons (seeds 20, 549, 617, 667) holding a
+                      local MILP whose node LPs stalled the interior point (HVP_MAXITER on a feasible
+                      problem); "exp_unique" marks the instances whose LP optimum is a unique vertex
+  l1batch_n10_N10.npz the benchmark's n = 10, N = 10 min_1_norm platoons (seeds 0..255), one vehicle
+                      (seed % 10) each: oracle status, cost and sequence only (no params)
 Run:  python tests/golden/make_golden.py [sweep | gear | admm | admm_l1 [n10] | admm_gear | gadmm | cent [n10 | l1] | configs admm|gadmm
-                                          | l1 | l1_rollout | l1_long]
+                                          | l1 | l1_rollout | l1_long | l1stall | l1batch]
 """
 
 from __future__ import annotations
@@ -180,6 +185,88 @@ def l1_long():
         save("l1_long_rollout_n4_N10.npz", 10, [800.0], O.Cfg(), params, roles, si, exp, method=1, quadratic=0)
     finally:
         O.set_method(O.METHOD_ENUMERATE)
+
+
+def _l1_bnb_init():
+    O.set_method(O.METHOD_BNB)
+
+
+def _l1_bnb_case(job):
+    """One min_1_norm oracle solve by branch and bound (worker of l1_stall / l1_batch)."""
+    N, p, r = job
+    x0, xf, xb, xl = split_params(p, N)
+    return O.solve_miqp(O.gear_pwa_system(800.0), O.Cfg(), N, int(r), x0, xf, xb, xl, quadratic=False)
+
+
+def _l1_bnb_solve(N, params, roles):
+    """solve_set's dictionary for min_1_norm instances, the oracle's branch and bound on every core."""
+    from multiprocessing import Pool
+
+    with Pool(min(16, os.cpu_count() or 1), initializer=_l1_bnb_init) as pool:
+        res = pool.map(_l1_bnb_case, [(N, p, r) for p, r in zip(params, roles)], chunksize=1)
+    return {"region": np.array([r.sigma if r.status == 0 else np.full(N, -1) for r in res]),
+            "u": np.array([r.u for r in res]), "x": np.array([r.x for r in res]),
+            "cost": np.array([r.cost for r in res]), "nodes": np.array([r.n_candidates for r in res]),
+            "status": np.array([r.status for r in res]), "certified": np.array([r.best_certified for r in res])}
+
+
+L1_STALL_SEEDS = (20, 549, 617, 667)  # platoons holding (seed, vehicle) (20, 1), (549, 6), (617, 4), (667, 7)
+
+
+def l1_stall():
+    """The n = 10, N = 10 min_1_norm platoons in which one local MILP (a slow front vehicle, a much
+    faster back vehicle: active w = 1e4 safe-distance hinges, a degenerate LP optimum) has node LPs on
+    which the interior point of hvp_l1.h stalled short of its stop test.  Whole platoons, oracle branch
+    and bound.  exp_unique: the oracle's u equals (1e-8) the vertex HiGHS returns for the oracle's own
+    LP of the winning sequence; false where the LP optimum is a face, whose points all price alike."""
+    from scipy.optimize import linprog
+
+    n = N = 10
+    P, R = [], []
+    for s in L1_STALL_SEEDS:
+        p, r = decent_instances(O.env_initial_state(n, s), N, leader_window(N))
+        P.append(p)
+        R.append(r)
+    params, roles = np.concatenate(P), np.concatenate(R)
+    exp = _l1_bnb_solve(N, params, roles)
+    assert (exp["status"] == 0).all(), exp["status"]
+    g = O.gear_pwa_system(800.0)
+    unique = np.zeros(len(roles), bool)
+    for j, (p, r) in enumerate(zip(params, roles)):
+        x0, xf, xb, xl = split_params(p, N)
+        _, q, _, A, b, G, h = O.export_qp(g, O.Cfg(), N, int(r), exp["region"][j], x0, xf, xb, xl, quadratic=False)
+        # HiGHS's choice ("highs", here its dual simplex) finds the oracle's own vertex even where the
+        # optimum is a face (seed 549, vehicle 6: every u within 0.54 prices alike); its interior point
+        # lands elsewhere on a face, so unique = both agree with the oracle
+        unique[j] = True
+        for method in ("highs", "highs-ipm"):
+            lp = linprog(q, A_ub=G, b_ub=h, A_eq=A, b_eq=b, bounds=[(None, None)] * len(q), method=method)
+            assert lp.status == 0, (j, lp.message)
+            unique[j] &= np.abs(lp.x[2 * N:3 * N] - exp["u"][j]).max() <= 1e-8  # z = [x_1 .. x_N | u | ...]
+    exp["unique"] = unique
+    save("l1stall_n10_N10.npz", N, [800.0], O.Cfg(), params, roles, np.zeros(len(roles), np.int32), exp, method=1,
+         quadratic=0)
+    print("faces (exp_unique false):", [(L1_STALL_SEEDS[j // n], j % n) for j in np.flatnonzero(~unique)])
+
+
+def l1_batch():
+    """One vehicle (seed % 10, bench.cpu_baseline's sampling rule) of each of the 256 benchmark platoons
+    (seeds 0..255, n = 10, N = 10, min_1_norm): the oracle's status, cost and sequence.  No params:
+    the tests rebuild them (decent_instances)."""
+    n = N = 10
+    seeds = np.arange(256)
+    index = seeds * n + seeds % n  # into the 2560 instances in platoon order
+    P, R = [], []
+    for s in seeds:
+        p, r = decent_instances(O.env_initial_state(n, int(s)), N, leader_window(N))
+        P.append(p[s % n])
+        R.append(r[s % n])
+    exp = _l1_bnb_solve(N, np.array(P), np.array(R))
+    assert (exp["status"] == 0).all(), np.flatnonzero(exp["status"] != 0)
+    np.savez_compressed(os.path.join(HERE, "l1batch_n10_N10.npz"), N=N, n=n, seeds=seeds.astype(np.int32),
+                        index=index.astype(np.int32), exp_status=exp["status"].astype(np.int32),
+                        exp_cost=exp["cost"], exp_region=exp["region"].astype(np.int32))
+    print(f"l1batch_n10_N10.npz: {len(seeds)} instances, optimal {int((exp['status'] == 0).sum())}")
 
 
 def gear_model():
@@ -660,6 +747,12 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "l1_long":
         l1_long()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "l1stall":
+        l1_stall()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "l1batch":
+        l1_batch()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "l1_rollout":
         l1_rollout()

@@ -132,6 +132,49 @@ def test_admm_l1_local_problem_on_gpu(gpu_available, name):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", LOCAL)
+def test_admm_l1_iteration_cap_sweep(gpu_available, name):
+    """The wave interior point's iteration cap swept (2 .. 40 and the default): short of its strict
+    stop test the solver may return a looser best iterate, whose primal price is no lower bound of a
+    node -- so whatever the cap, an instance is HVP_MAXITER or the fixture's answer (status,
+    sequence, cost 1e-9), never HVP_OPTIMAL with another sequence or a worse cost; at the default
+    cap every instance is the fixture's."""
+    from hvp import _abi
+    from hvp.solver import BatchSolver
+
+    import torch
+
+    fx = load(name)
+    N, B = int(fx["N"]), len(fx["roles"])
+    ce = fx["exp_cost"]
+    dev = torch.device("cuda", 0)
+    tr = torch.from_numpy(np.ascontiguousarray(fx["roles"].astype(np.int32))).to(dev)
+    tp = torch.from_numpy(np.ascontiguousarray(fx["params"], dtype=np.float64)).to(dev)
+    for cap in (2, 4, 6, 8, 10, 12, 14, 16, 20, 25, 30, 40, 0):
+        prob = _problem(N, float(fx["rho"]), _cfg(fx))
+        prob.max_iter = cap
+        # (with a small cap no node LP resolves and nothing is pruned: the searches that outgrow their
+        # share of the workspace, HVP_OVERFLOW, are re-solved on their own as BatchSolver.solve does)
+        s = BatchSolver(prob, [_system()])
+        out = s.alloc_outputs(B, dev)
+        out["x_front"] = torch.zeros((B, 2, N + 1), dtype=torch.float64, device=dev)
+        out["x_back"] = torch.zeros((B, 2, N + 1), dtype=torch.float64, device=dev)
+        s.solve_admm_device(torch.zeros(B, dtype=torch.int32, device=dev), tr, tp, out, retry_overflow=True)
+        torch.cuda.synchronize(dev)
+        status, region, cost = (out[k].cpu().numpy() for k in ("status", "region", "cost"))
+        unres = status == _abi.MAXITER
+        assert not (unres & (fx["exp_status"] != 0)).any(), cap  # an infeasible instance stays infeasible
+        done = ~unres
+        assert np.array_equal(status[done], fx["exp_status"][done]), (cap, status)
+        ok = done & (fx["exp_status"] == 0)
+        assert np.array_equal(region[ok], fx["exp_region"][ok]), cap
+        err = np.abs(cost[ok] - ce[ok]) / np.maximum(1.0, np.abs(ce[ok]))
+        assert np.all(err <= 1e-9), (cap, err.max())
+        if cap == 0:
+            assert done.all()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["admm_l1_steps_n4_N5.npz", "admm_l1_steps_n10_N10.npz"])
 def test_admm_l1_coordinator_steps_match_oracle(gpu_available, name):
     """Closed-loop time steps of the min_1_norm naive-ADMM coordinator: the device engine (batched

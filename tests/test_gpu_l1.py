@@ -318,3 +318,96 @@ def test_l1_status_infeasible_and_unresolved(gpu_available, N, method):
     capped = tables.problem(N, quadratic_cost=False, method=method, max_iter=2)
     res = BatchSolver(capped, [table]).solve(sysi, role, params)
     assert res.status[0] == _abi.INFEASIBLE and (res.status[1:] == _abi.MAXITER).all()
+
+
+def test_l1_stall_fixture_on_gpu(gpu_available):
+    """The four n = 10, N = 10 platoons holding a local MILP on which the wave interior point stalls
+    (tests/test_hostref.py test_l1_stall_instances_resolve): the device -- k_l1_bound, then the
+    level's unresolved LPs by the simplex (k_l1_retry) -- returns the oracle's answers for all 40."""
+    from hvp import _abi
+    from hvp.solver import BatchSolver
+    from test_hostref import _assert_l1_answers
+
+    fx = load("l1stall_n10_N10.npz")
+    prob, systems = product_problem(fx)
+    assert prob.quadratic_cost == 0
+    prob.method = _abi.METHOD_BNB
+    res = BatchSolver(prob, systems).solve(fx["sys"], fx["roles"], fx["params"])
+    out = dict(status=res.status, region=res.region, cost=res.cost, u=res.u, x=res.x)
+    _assert_l1_answers(fx, out, fx["exp_unique"])
+
+
+def test_l1_wave_batch_n10_N10(gpu_available):
+    """The benchmark's n = 10, N = 10 min_1_norm step (platoon seeds 0..255, 2,560 local MILPs, every
+    node LP by the wave interior point): deterministic, every instance HVP_OPTIMAL (seed 20's vehicle 1
+    stalled the interior point), every answer feasible with its reported cost the min_1_norm
+    objective of its own (x, u), and the vehicle (seed % 10) of each platoon equal to the oracle's
+    branch and bound (l1batch_n10_N10.npz) in sequence and cost."""
+    import torch
+
+    from hvp import tables
+    from hvp.models import PwaGearVehicle
+    from hvp.solver import BatchSolver
+    from test_hostref import _bench_instances
+
+    fb = load("l1batch_n10_N10.npz")
+    N = int(fb["N"])
+    params, roles = _bench_instances(fb["seeds"], int(fb["n"]), N)
+    veh = PwaGearVehicle(800.0)
+    s = BatchSolver(tables.problem(N, quadratic_cost=False), [tables.system_from_dict(veh.get_discrete_system(1),
+                                                                                       tables.gears_of(veh))])
+    dev = torch.device("cuda", 0)
+    tp, tr = torch.from_numpy(params).to(dev), torch.from_numpy(roles).to(dev)
+    ts = torch.zeros(len(roles), dtype=torch.int32, device=dev)
+    a = s.solve_device(ts, tr, tp, retry_overflow=True)
+    failed_bounds = int(s.stats().n_failed_bounds)
+    b = s.solve_device(ts, tr, tp, retry_overflow=True)
+    torch.cuda.synchronize()
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    st = a["status"].cpu().numpy()
+    # (an interior node the interior point and the simplex both leave unresolved only stops pruning)
+    assert (st == 0).all(), (np.flatnonzero(st), st[st != 0], f"n_failed_bounds {failed_bounds}")
+    u, x, reg = a["u"].cpu().numpy(), a["x"].cpu().numpy(), a["region"].cpu().numpy()
+    cost = a["cost"].cpu().numpy()
+    assert np.abs(u).max() <= 1 + 1e-9
+    v = x[:, 1, :]
+    assert v[:, 1:].min() >= 3.94 - 1e-9 and v[:, 1:].max() <= 45.84 + 1e-9
+    dv = np.diff(v, axis=1)
+    assert dv.min() >= -2 - 1e-9 and dv.max() <= 2.5 + 1e-9
+    lim = np.array([-np.inf, 9.235, 12.855, 16.93, 22.92, 23.315, 32.47, np.inf])
+    assert np.all(v[:, :N] >= lim[reg] - 1e-7) and np.all(v[:, :N] <= lim[reg + 1] + 1e-7)
+    g = O.gear_pwa_system(800.0)
+    assert np.abs(g["A"][reg, 1, 1] * v[:, :N] + g["B"][reg, 1] * u + g["c"][reg, 1] - v[:, 1:]).max() <= 1e-9
+    assert np.all(np.abs(_l1_cost(x, u, params, roles, N) - cost) <= 1e-9 * np.maximum(1, np.abs(cost)))
+    idx = fb["index"]
+    assert (fb["exp_status"] == 0).all()
+    assert np.array_equal(reg[idx], fb["exp_region"])
+    ce = fb["exp_cost"]
+    assert np.all(np.abs(cost[idx] - ce) <= 1e-9 * np.maximum(1, np.abs(ce))), np.abs(cost[idx] - ce).max()
+
+
+def test_l1_iteration_cap_sweep_on_gpu(gpu_available):
+    """The interior point's iteration cap swept over the N = 10 fixture on the device (as
+    tests/test_hostref.py test_l1_iteration_cap_sweep): an instance is HVP_MAXITER or the fixture's
+    answer, never HVP_OPTIMAL with another sequence or a worse cost; the default cap resolves all."""
+    from hvp import _abi
+    from hvp.solver import BatchSolver
+    from test_hostref import L1_CAPS
+
+    fx = load("l1_long_n5_N10.npz")
+    ce = fx["exp_cost"]
+    for cap in L1_CAPS:
+        prob, systems = product_problem(fx)
+        prob.method = _abi.METHOD_BNB
+        prob.max_iter = cap
+        res = BatchSolver(prob, systems).solve(fx["sys"], fx["roles"], fx["params"])
+        unres = res.status == _abi.MAXITER
+        assert not (unres & (fx["exp_status"] != 0)).any(), cap
+        done = ~unres
+        assert np.array_equal(res.status[done], fx["exp_status"][done]), cap
+        ok = done & (fx["exp_status"] == 0)
+        assert np.array_equal(res.region[ok], fx["exp_region"][ok]), cap
+        assert np.all(np.abs(res.cost[ok] - ce[ok]) <= 1e-9 * np.maximum(1, np.abs(ce[ok]))), cap
+        if cap == 0:
+            assert done.all()

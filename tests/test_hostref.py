@@ -27,7 +27,7 @@ def hostref():
     return ctypes.CDLL(_abi.HOSTREF_PATH)
 
 
-def run(L, prob, systems, fx):
+def run(L, prob, systems, fx, nthreads=4):
     from hvp import _abi
 
     N = int(fx["N"])
@@ -41,7 +41,7 @@ def run(L, prob, systems, fx):
     roles = np.ascontiguousarray(fx["roles"].astype(np.int32))
     rc = L.hvp_hostref_solve_batch(ctypes.byref(prob), S, B, f(sys_idx), f(roles), f(params), f(out["u"]),
                                    f(out["x"]), f(out["region"]), f(out["cost"]), f(out["status"]), f(out["nodes"]),
-                                   f(out["iters"]), 4)
+                                   f(out["iters"]), nthreads)
     assert rc == 0
     return out
 
@@ -220,3 +220,135 @@ def test_l1_oracle_repricing_of_simplex_vertices(hostref):
                          p[2 + K:2 + 2 * K].reshape(2, -1), p[2 + 2 * K:].reshape(2, -1), r["x"][j], r["u"][j])
         ce = float(fx["exp_cost"][j])
         assert abs(val - ce) <= 1e-9 * max(1.0, abs(ce)), (j, val, ce)
+
+
+def _assert_l1_answers(fx, out, unique):
+    """Statuses and regions exact, cost 1e-9 relative; u 1e-6 and x 1e-4 where the LP optimum is a
+    unique vertex (`unique`); elsewhere (a face: its points price alike) the returned (x, u), priced by
+    the oracle's own LP of that sequence (test_gpu_l1.reprice_l1), within 1e-8 relative of the
+    optimum -- test_l1_platoon_batch's bar for faces -- and |u| <= 1."""
+    from test_gpu_l1 import reprice_l1
+
+    import oracle as O
+
+    N = int(fx["N"])
+    assert np.array_equal(out["status"], fx["exp_status"]), np.flatnonzero(out["status"] != fx["exp_status"])
+    assert (fx["exp_status"] == 0).all()
+    assert np.array_equal(out["region"], fx["exp_region"])
+    c, ce = out["cost"], fx["exp_cost"]
+    assert np.all(np.abs(c - ce) <= 1e-9 * np.maximum(1, np.abs(ce))), np.abs(c - ce).max()
+    assert np.abs(out["u"][unique] - fx["exp_u"][unique]).max() <= 1e-6
+    assert np.abs(out["x"][unique] - fx["exp_x"][unique]).max() <= 1e-4
+    g = O.gear_pwa_system(800.0)
+    K = 2 * (N + 1)
+    for j in np.flatnonzero(~unique):
+        p = fx["params"][j]
+        val = reprice_l1(g, O.Cfg(), N, int(fx["roles"][j]), out["region"][j], p[:2], p[2:2 + K].reshape(2, -1),
+                         p[2 + K:2 + 2 * K].reshape(2, -1), p[2 + 2 * K:].reshape(2, -1), out["x"][j], out["u"][j])
+        assert abs(val - ce[j]) <= 1e-8 * max(1.0, abs(ce[j])), (j, val, ce[j])
+        assert np.abs(out["u"][j]).max() <= 1.0 + 1e-9
+
+
+def test_l1_stall_instances_resolve(hostref):
+    """The four n = 10, N = 10 platoons (seeds 20, 549, 617, 667) in which one local MILP made the
+    interior point of hvp_l1.h stall (gap collapsed, dual residual stuck: HVP_MAXITER with no
+    sequence for a feasible problem).  The host build -- the device's rule: the level's unresolved LPs
+    go to the simplex of hvp_lp.h -- returns the oracle's status, sequence and cost for all 40."""
+    fx = load("l1stall_n10_N10.npz")
+    assert not fx["exp_unique"][16]  # (549, 6): the LP optimum is a face
+    prob, systems = product_problem(fx)
+    assert prob.quadratic_cost == 0
+    prob.method = 2  # HVP_METHOD_BNB
+    out = run(hostref, prob, systems, fx)
+    _assert_l1_answers(fx, out, fx["exp_unique"])
+
+
+def _bench_instances(seeds, n=10, N=10):
+    """bench.make_inputs(seeds, n, N): the local MILPs of the benchmark's platoons, in platoon order."""
+    import oracle as O
+    from instances import decent_instances, leader_window
+
+    P, R = [], []
+    for s in seeds:
+        p, r = decent_instances(O.env_initial_state(n, int(s)), N, leader_window(N))
+        P.append(p)
+        R.append(r)
+    return np.concatenate(P), np.concatenate(R)
+
+
+@pytest.mark.slow
+def test_l1_census_n10_N10(hostref):
+    """Census of the benchmark's n = 10, N = 10 min_1_norm line (platoon seeds 0..255, 2,560 local
+    MILPs) on the host build: every instance resolves, and the vehicle (seed % 10) of each platoon
+    equals the oracle's branch and bound (l1batch_n10_N10.npz) in sequence and cost."""
+    from hvp import tables
+    from hvp.models import PwaGearVehicle
+
+    fb = load("l1batch_n10_N10.npz")
+    N = int(fb["N"])
+    assert (fb["exp_status"] == 0).all()
+    params, roles = _bench_instances(fb["seeds"], int(fb["n"]), N)
+    veh = PwaGearVehicle(800.0)
+    table = tables.system_from_dict(veh.get_discrete_system(1), tables.gears_of(veh))
+    prob = tables.problem(N, quadratic_cost=False, method=2)
+    fx = dict(N=N, roles=roles, params=params, sys=np.zeros(len(roles), np.int32))
+    out = run(hostref, prob, [table], fx, nthreads=min(16, os.cpu_count() or 1))
+    assert (out["status"] == 0).all(), np.flatnonzero(out["status"])
+    idx = fb["index"]
+    assert np.array_equal(out["region"][idx], fb["exp_region"])
+    c, ce = out["cost"][idx], fb["exp_cost"]
+    assert np.all(np.abs(c - ce) <= 1e-9 * np.maximum(1, np.abs(ce))), np.abs(c - ce).max()
+
+
+L1_CAPS = (2, 4, 6, 8, 10, 12, 14, 16, 20, 25, 30, 40, 0)  # 0: the default cap
+
+
+@pytest.mark.slow
+def test_l1_iteration_cap_sweep(hostref):
+    """The interior point's iteration cap swept over the N = 10 fixture: whatever the cap, an instance
+    is HVP_MAXITER or the fixture's answer (status, sequence, cost 1e-9) -- never HVP_OPTIMAL with
+    another sequence or a worse cost; at the default cap every instance is the fixture's.  (Slow: under
+    a small cap no LP resolves, nothing is pruned and every sequence's leaf is tried.)"""
+    fx = load("l1_long_n5_N10.npz")
+    ce = fx["exp_cost"]
+    for cap in L1_CAPS:
+        prob, systems = product_problem(fx)
+        prob.method = 2
+        prob.max_iter = cap
+        out = run(hostref, prob, systems, fx, nthreads=min(16, os.cpu_count() or 1))
+        unres = out["status"] == 2  # HVP_MAXITER
+        assert not (unres & (fx["exp_status"] != 0)).any(), cap  # the infeasible ones stay infeasible
+        done = ~unres
+        assert np.array_equal(out["status"][done], fx["exp_status"][done]), cap
+        ok = done & (fx["exp_status"] == 0)
+        assert np.array_equal(out["region"][ok], fx["exp_region"][ok]), cap
+        assert np.all(np.abs(out["cost"][ok] - ce[ok]) <= 1e-9 * np.maximum(1, np.abs(ce[ok]))), cap
+        if cap == 0:
+            assert done.all()
+
+
+def test_admm_l1_unsupported_on_host(hostref):
+    """The naive-ADMM min_1_norm local problem (copies as LP variables) exists on the device only:
+    the host build refuses it (HVP_E_UNSUPPORTED) instead of solving the decentralised LP on a params
+    row of another layout."""
+    from hvp import _abi
+    from test_admm_l1 import _cfg, _problem, _system
+
+    fx = load("admm_l1_local_N5.npz")
+    N, B = int(fx["N"]), len(fx["roles"])
+    prob = _problem(N, float(fx["rho"]), _cfg(fx))
+    assert prob.quadratic_cost == 0 and prob.formulation == _abi.FORM_ADMM
+    S = (_abi.HvpSystem * 1)(_system())
+    f = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    u, x, xf, xb = np.zeros((B, N)), np.zeros((B, 2, N + 1)), np.zeros((B, 2, N + 1)), np.zeros((B, 2, N + 1))
+    region, cost = np.zeros((B, N), np.int8), np.zeros(B)
+    status, nodes, iters = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    params = np.ascontiguousarray(fx["params"])
+    roles = np.ascontiguousarray(fx["roles"].astype(np.int32))
+    si = np.zeros(B, np.int32)
+    rc = hostref.hvp_hostref_solve_admm_batch(ctypes.byref(prob), S, B, f(si), f(roles), f(params), f(u), f(x),
+                                              f(region), f(cost), f(status), f(nodes), f(iters), f(xf), f(xb), 1)
+    assert rc == -3  # HVP_E_UNSUPPORTED
+    rc = hostref.hvp_hostref_solve_batch(ctypes.byref(prob), S, B, f(si), f(roles), f(params), f(u), f(x), f(region),
+                                         f(cost), f(status), f(nodes), f(iters), 1)
+    assert rc == -3
