@@ -787,7 +787,7 @@ HVP_HD inline bool pbox_ok(const LaneQp<N, M>& q) {
 
 // tail relaxation of one undecided step (defined below with reach_step)
 HVP_HD inline int relax_step(const hvp_system& S, const Consts& C, int k, double lo, double hi, double& nlo,
-                             double& nhi, double& bmax, bool& dead);
+                             double& nhi, double& bmax, bool& dead, unsigned* reach = nullptr);
 
 // ------------------------------------------------------------------ problem setup
 // The lane QP of (instance params (x0, x_front, x_back, leader_x), region code) is assembled in
@@ -897,11 +897,14 @@ HVP_HD inline bool setup_scalars(LaneQp<N, M>& q, const hvp_system& S, int role,
     return q.P1 >= S.pmin - 1e-9 * (1.0 + fabs(S.pmin)) && q.P1 <= S.pmax + 1e-9 * (1.0 + fabs(S.pmax));
 }
 
-// per-node part (see above); q.H, q.f, q.C0 hold the tracking part on entry
+// per-node part (see above); q.H, q.f, q.C0 hold the tracking part on entry.  kmask (optional)
+// receives the regions step K can take from [rlo, rhi], as relax_step finds them: the child set
+// of the branch-and-bound node (0 when there is no step K to relax)
 template <int N, class M>
 HVP_HD inline void setup_input(LaneQp<N, M>& q, const hvp_system& S, const Consts& C, uint64_t code, int K = N,
-                               double rlo = 0.0, double rhi = -1.0) {
+                               double rlo = 0.0, double rhi = -1.0, unsigned* kmask = nullptr) {
     const double v0 = q.v0;
+    if (kmask) *kmask = 0;
     double a[N], b[N], c[N];
     unsigned ucost = 0;      // steps carrying their input cost
     bool relax = rlo <= rhi;  // [rlo, rhi] = exact interval of v_K (branch and bound)
@@ -917,7 +920,9 @@ HVP_HD inline void setup_input(LaneQp<N, M>& q, const hvp_system& S, const Const
         double bm = 1.0, nlo = S.vmin, nhi = S.vmax;
         if (!fixed && relax) {
             bool dead;
-            vr = relax_step(S, C, k, rlo, rhi, nlo, nhi, bm, dead);
+            unsigned reach;
+            vr = relax_step(S, C, k, rlo, rhi, nlo, nhi, bm, dead, &reach);
+            if (kmask && k == K) *kmask = reach;
             relax = !dead;
             rlo = nlo;
             rhi = nhi;
@@ -1021,11 +1026,32 @@ HVP_HD inline T* opaque_ptr(T* p) {
     return p;
 }
 
+// The same for direct_cost's two operands, through a zero byte offset the compiler cannot see
+// (HVP_DC_OPAQUE_PTR=1: through the pointers themselves, A/B).  A laundered pointer comes back
+// generic and every load through it a flat load; a base plus an unknown offset keeps its address
+// space, so the params row stays global loads and a table staged in LDS stays LDS reads.
+#ifndef HVP_DC_OPAQUE_PTR
+#define HVP_DC_OPAQUE_PTR 0
+#endif
+HVP_HD inline int opaque_zero() {
+    int z = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(z));
+#endif
+    return z;
+}
+
 template <int N, class M>
 HVP_HD inline double direct_cost(const LaneQp<N, M>& q, const hvp_system& S_in, const Consts& C, int role,
                                  const double* prm_in, uint64_t code, int K = N) {
+#if HVP_DC_OPAQUE_PTR
     const double* prm = opaque_ptr(prm_in);
     const hvp_system& S = *opaque_ptr(&S_in);
+#else
+    const int z = opaque_zero();
+    const double* prm = reinterpret_cast<const double*>(reinterpret_cast<const char*>(prm_in) + z);
+    const hvp_system& S = *reinterpret_cast<const hvp_system*>(reinterpret_cast<const char*>(&S_in) + z);
+#endif
     const double* xf = prm + 2;
     const double* xb = prm + 2 + 2 * (N + 1);
     const double* xl = prm + 2 + 4 * (N + 1);
@@ -1113,17 +1139,20 @@ HVP_HD inline bool bnb_child(const hvp_system& S, const Consts& C, int k, double
 // when all of them share the velocity dynamics (a, c) with b > 0 (and umin <= 0 <= umax), the
 // VIRTUAL region of the step: dynamics (a, bmax, c) with the input box and cost on
 // s = u b_r / bmax, a valid relaxation of every region's input (|s| <= |u|).  Returns the first
-// such region (virt) or -1; dead = no region is reachable (the relaxation stops there).
+// such region (virt) or -1; dead = no region is reachable (the relaxation stops there).  reach
+// (optional) receives the mask of the reachable regions: the node's child set when k is its depth.
 HVP_HD inline int relax_step(const hvp_system& S, const Consts& C, int k, double lo, double hi, double& nlo,
-                             double& nhi, double& bmax, bool& dead) {
+                             double& nhi, double& bmax, bool& dead, unsigned* reach) {
     nlo = 1e300;
     nhi = -1e300;
     bmax = 0.0;
     int first = -1;
+    unsigned mask = 0;
     bool shared = S.umin <= 0.0 && S.umax >= 0.0 && S.umax > S.umin;
     for (int r = 0; r < S.n_regions; ++r) {
         double a, b;
         if (!bnb_child(S, C, k, lo, hi, r, &a, &b)) continue;
+        mask |= 1u << r;
         nlo = fmin(nlo, a);
         nhi = fmax(nhi, b);
         if (first < 0) first = r;
@@ -1132,6 +1161,7 @@ HVP_HD inline int relax_step(const hvp_system& S, const Consts& C, int k, double
         bmax = fmax(bmax, S.b[r]);
     }
     dead = first < 0;
+    if (reach) *reach = mask;
     return shared && !dead ? first : -1;
 }
 

@@ -2515,11 +2515,6 @@ __global__ __launch_bounds__(kBnbBlock<N>) void k_lp_bound(int k, const hvp_syst
 #ifndef HVP_REFILL_BYVAL
 #define HVP_REFILL_BYVAL 1
 #endif
-#if HVP_REFILL_BYVAL
-#define HVP_REFILL_LAUNCH_ARGS(wsp, wsval) wsval
-#else
-#define HVP_REFILL_LAUNCH_ARGS(wsp, wsval) wsp, h->d_consts, wsval
-#endif
 #ifndef HVP_REFILL_WS_ARG
 #define HVP_REFILL_WS_ARG 0
 #endif
@@ -2622,7 +2617,8 @@ __global__ __launch_bounds__(kBlock) void k_bnb_dive_prep(int B, const hvp_syste
 // the node QP of instance inst from the per-instance part + the node's regions / relaxation
 template <int N, class Q>
 __device__ inline bool setup_node(Q& q, const hvp_system& S, const hvp::Consts& C, const Workspace& ws, int inst,
-                                  int rl, const double* prm, uint64_t code, int K, double rlo, double rhi) {
+                                  int rl, const double* prm, uint64_t code, int K, double rlo, double rhi,
+                                  unsigned* kmask = nullptr) {
     constexpr int NT = N * (N + 1) / 2;
     const double* o = static_cast<const double*>(__builtin_assume_aligned(ws.iq + (size_t)inst * kIqStride<N>, 128));
     const bool ok = hvp::setup_scalars<N>(q, S, rl, prm[0], prm[1]);
@@ -2636,7 +2632,7 @@ __device__ inline bool setup_node(Q& q, const hvp_system& S, const hvp::Consts& 
         q.mem.set(hvp::F_HB, j, o[NT + 2 * N - 1 + j]);
     }
     q.C0 = 0.0;  // not used by the active-set path (costs come from direct_cost)
-    hvp::setup_input<N>(q, S, C, code, K, rlo, rhi);
+    hvp::setup_input<N>(q, S, C, code, K, rlo, rhi, kmask);
     return ok;
 }
 
@@ -2967,16 +2963,47 @@ __device__ inline const T* uniform_opaque(const T* p) {
 // loaded inside the event through uniform_opaque pointers.  (With both structures as kernel
 // arguments live across the loop, 128 SGPRs spilled into two VGPRs' lanes and 35 dwords of VGPRs
 // into scratch.)
+//
+// System tables: the event's region loops (relax_step, bnb_child, bnb_put_children) and
+// direct_cost read hvp_system fields tens of times per node, each a dependent per-lane load
+// (systems[sys[inst]]).  STAGE: the block copies the handle's n_sys tables into LDS at entry and
+// the event indexes that copy by sys[inst] (a batch may mix systems).  At most kRefillSysCap
+// tables: at N = 5 the per-lane rows take 71,680 B of the 81,920 B a block may use with two
+// blocks per CU, and 8 tables are 6,144 B.  A handle with more systems runs the STAGE = false
+// instantiation, which reads them from global memory (launch_refill).
+// HVP_REFILL_SYS_LDS=0 builds only the global-memory instantiation (A/B).
+// HVP_REFILL_CHILD_ONCE: the node's child set is the mask its set-up's relax_step at step k
+// found, kept in a lane register until the write-back, instead of bnb_children's second pass
+// over the regions there (the same calls with the same arguments; 0: A/B).
+#ifndef HVP_REFILL_SYS_LDS
+#define HVP_REFILL_SYS_LDS 1
+#endif
+#ifndef HVP_REFILL_CHILD_ONCE
+#define HVP_REFILL_CHILD_ONCE 1
+#endif
+constexpr int kRefillSysCap = 8;
 #if HVP_REFILL_BYVAL
 // (round 3's kernel body: the descriptor and the constants as by-value kernel arguments, the
 // level list hoisted)
-template <int N>
+template <int N, bool STAGE>
 __global__ __launch_bounds__(kBnbBlock<N>) __attribute__((amdgpu_waves_per_eu(HVP_REFILL_WAVES)))
-void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, const int32_t* __restrict__ sys,
+void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys, const int32_t* __restrict__ sys,
                         const int32_t* __restrict__ role, const double* __restrict__ params, hvp::Consts C,
                         Workspace ws) {
     constexpr int BS = kBnbBlock<N>;
     static_assert(N <= HVP_MAX_N_ENUM, "lane refill is the N <= 8 path");
+    const hvp_system* tab = systems;  // the tables the event reads
+    if constexpr (STAGE) {
+        __shared__ hvp_system s_sys[kRefillSysCap];
+        static_assert(sizeof(hvp_system) % sizeof(unsigned long long) == 0, "copied in 8-byte words");
+        constexpr int kWords = (int)(sizeof(hvp_system) / sizeof(unsigned long long));
+        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(systems);
+        unsigned long long* dstw = reinterpret_cast<unsigned long long*>(s_sys);
+        const int nw = (n_sys < kRefillSysCap ? n_sys : kRefillSysCap) * kWords;
+        for (int i = threadIdx.x; i < nw; i += BS) dstw[i] = src[i];
+        __syncthreads();
+        tab = s_sys;
+    }
     const int dst = k & 1;
     const LevelList lvl = level_list(ws, k);
     const long long total = lvl.count();
@@ -2988,6 +3015,7 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, const int
     long long t = -1;  // node of the lane
     int inst = 0, stage = RS_IDLE, fail = 0;  // (RS_PASS: fail holds the pass-through node's steps)
     uint64_t code = 0;
+    unsigned nmask = 0;  // regions the lane's node can take at step k (its set-up's relax_step)
     bool exhausted = false;
     unsigned long long iter_sum = 0, pass_n = 0;
 #ifdef HVP_REFILL_PROF  // diagnostics build: event / trip cycles and busy lane-trips per wave
@@ -3027,11 +3055,11 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, const int
                 clb = ws.nd_lb[dst][t];
                 csteps = fail;
                 if (!(ws.inst_flag[inst] & 2) && !hvp::bnb_pruned(clb, inc_of(ws, inst)))
-                    cmask = bnb_children(systems[sys[inst]], C, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
+                    cmask = bnb_children(tab[sys[inst]], C, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
             } else if (done) {
                 const int st = stage == RS_OPT ? g.verify(C, nullptr) : fail;
                 const bool ok = st == hvp::GI_OK;
-                const double c = ok ? hvp::direct_cost<N>(q, systems[sys[inst]], C, role[inst],
+                const double c = ok ? hvp::direct_cost<N>(q, tab[sys[inst]], C, role[inst],
                                                           params + (size_t)inst * C.stride, code, k)
                                     : 0.0;
                 iter_sum += (unsigned long long)g.iter;
@@ -3048,15 +3076,20 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, const int
                 // the incumbent only changes at the leaves (level N): below N this pruning test
                 // sees the value a separate expand kernel would
                 clb = ok ? c : -1e300;
-                if (k < N && !(ws.inst_flag[inst] & 2) && !hvp::bnb_pruned(clb, inc_of(ws, inst)))
-                    cmask = bnb_children(systems[sys[inst]], C, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
+                if (k < N && !(ws.inst_flag[inst] & 2) && !hvp::bnb_pruned(clb, inc_of(ws, inst))) {
+#if HVP_REFILL_CHILD_ONCE
+                    cmask = nmask;
+#else
+                    cmask = bnb_children(tab[sys[inst]], C, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
+#endif
+                }
             }
             if (k < N) {
                 unsigned long long limit;
                 const unsigned long long off =
                     split_reserve(ws, k + 1, __popc(cmask), csteps > 0 ? csteps : 0, lane, limit);
                 if (cmask)
-                    pass_n += bnb_put_children(ws, k + 1, off, limit, cmask, inst, systems[sys[inst]], C, code,
+                    pass_n += bnb_put_children(ws, k + 1, off, limit, cmask, inst, tab[sys[inst]], C, code,
                                                ws.nd_lo[dst][t], ws.nd_hi[dst][t], clb, k + 1 < N ? csteps : -1);
 #ifdef HVP_REFILL_PROF
                 pf_rs += __builtin_amdgcn_s_memtime() - pf_e0;
@@ -3092,9 +3125,9 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, const int
                             code &= kPassCode;
                             stage = RS_PASS;
                         } else {
-                            setup_node<N>(q, systems[sys[inst]], C, ws, inst, role[inst],
+                            setup_node<N>(q, tab[sys[inst]], C, ws, inst, role[inst],
                                           params + (size_t)inst * C.stride, code, k, ws.nd_lo[dst][mine],
-                                          ws.nd_hi[dst][mine]);
+                                          ws.nd_hi[dst][mine], HVP_REFILL_CHILD_ONCE ? &nmask : nullptr);
                             stage = g.init(q) == hvp::GI_OK ? RS_SCAN : RS_FAIL;
                             fail = hvp::GI_FAIL_CHOL;
                         }
@@ -3906,6 +3939,29 @@ hipError_t node_records(hvp_handle* h, int B, Workspace& ws) {
     return hipSuccess;
 }
 
+// one launch of the refill kernel over level k's list; which = 0: the level lists, 1: the dive list
+// (hvp_handle::ws_up).  The instantiation that stages the system tables in LDS when the handle's
+// systems fit its cap, else the one that reads them from global memory.
+template <int N>
+void launch_refill(hvp_handle* h, int grid, size_t lds, hipStream_t st, int k, const int32_t* sys,
+                   const int32_t* role, const double* params, int which) {
+    constexpr int BS = kBnbBlock<N>;
+#if HVP_REFILL_BYVAL
+#if HVP_REFILL_SYS_LDS
+    if (h->n_systems <= kRefillSysCap) {
+        hipLaunchKernelGGL((k_bnb_bound_refill<N, true>), dim3(grid), dim3(BS), lds, st, k, h->d_sys, h->n_systems,
+                           sys, role, params, h->C, h->ws_up[which]);
+        return;
+    }
+#endif
+    hipLaunchKernelGGL((k_bnb_bound_refill<N, false>), dim3(grid), dim3(BS), lds, st, k, h->d_sys, h->n_systems, sys,
+                       role, params, h->C, h->ws_up[which]);
+#else
+    hipLaunchKernelGGL(k_bnb_bound_refill<N>, dim3(grid), dim3(BS), lds, st, k, h->d_sys, sys, role, params, h->C,
+                       h->d_ws + which, h->d_consts, h->ws_up[which]);
+#endif
+}
+
 template <int N>
 int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, const double* params, double* u_out,
                double* x_out, int8_t* region_out, int8_t* gear_out, double* cost_out, int32_t* status_out,
@@ -4057,14 +4113,12 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
                                      ((unsigned long long)ws.cap >> ws.split_shift) >= (unsigned long long)B;
             if (root_refill) {
                 const int g_root = (int)std::min<long long>((B + BS - 1) / BS, (long long)h->n_cu * kRefillBlocksPerCu);
-                hipLaunchKernelGGL(k_bnb_bound_refill<N>, dim3(g_root), dim3(BS), lds, st, 0, h->d_sys, sys, role,
-                                   params, h->C, HVP_REFILL_LAUNCH_ARGS(h->d_ws, h->ws_up[0]));
+                launch_refill<N>(h, g_root, lds, st, 0, sys, role, params, 0);
                 HIP_TRY(hipGetLastError());
                 hipLaunchKernelGGL(k_bnb_dive_prep<N>, dim3(grid_for(B)), dim3(kBlock), 0, st, B, h->d_sys, sys, params,
                                    h->C, ws);
                 HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(k_bnb_bound_refill<N>, dim3(g_root), dim3(BS), lds, st, N, h->d_sys, sys, role,
-                                   params, h->C, HVP_REFILL_LAUNCH_ARGS(h->d_ws + 1, h->ws_up[1]));
+                launch_refill<N>(h, g_root, lds, st, N, sys, role, params, 1);
             } else {
                 // (one lane per instance, 1 wave per SIMD)
                 hipLaunchKernelGGL((k_bnb_root<N, false>), dim3((B + BS - 1) / BS), dim3(BS), lds, st, B, h->d_sys,
@@ -4121,8 +4175,7 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
                 // persistent waves: 2 blocks per CU, every wave refills its lanes until the level is done
                 const int g_refill = (int)std::min<long long>((h->ws.cap + BS - 1) / BS,
                                                               (long long)h->n_cu * kRefillBlocksPerCu);
-                hipLaunchKernelGGL(k_bnb_bound_refill<N>, dim3(g_refill), dim3(BS), lds, st, k, h->d_sys, sys, role,
-                                   params, h->C, HVP_REFILL_LAUNCH_ARGS(h->d_ws, h->ws_up[0]));
+                launch_refill<N>(h, g_refill, lds, st, k, sys, role, params, 0);
             }
         }
         HIP_TRY(hipGetLastError());
