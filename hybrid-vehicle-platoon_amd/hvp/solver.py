@@ -244,9 +244,10 @@ class BatchSolver:
         return params, roles
 
     # -------------------------------------------------------------- fixed-control evaluation
-    def evaluate_device(self, sys_idx, roles, params, gears, u, stream=None) -> dict:
+    def evaluate_device(self, sys_idx, roles, params, gears, u, stream=None, want_x: bool = True) -> dict:
         """Cost of fixed controls u (B, N) and gear labels (B, N) on the device (hvp_evaluate_batch:
-        MpcGear.evaluate_cost, mpcs/mpc_gear.py:137-170).  Returns cost, status, x."""
+        MpcGear.evaluate_cost, mpcs/mpc_gear.py:137-170).  Returns cost, status, x (want_x=False:
+        the ABI's x_out = NULL, no trajectory is written or returned)."""
         import torch
 
         B = int(roles.shape[0])
@@ -255,18 +256,19 @@ class BatchSolver:
             if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != B * self.N:
                 raise ValueError(f"{name} must be a contiguous CUDA ({B}, {self.N}) tensor of dtype {dt}")
         out = {"cost": torch.empty(B, dtype=torch.float64, device=dev),
-               "status": torch.empty(B, dtype=torch.int32, device=dev),
-               "x": torch.empty((B, 2, self.N + 1), dtype=torch.float64, device=dev)}
+               "status": torch.empty(B, dtype=torch.int32, device=dev)}
+        if want_x:
+            out["x"] = torch.empty((B, 2, self.N + 1), dtype=torch.float64, device=dev)
         if stream is None:
             stream = torch.cuda.current_stream(dev)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
         rc = self._lib.hvp_evaluate_batch(self._h, B, ptr(sys_idx), ptr(roles), ptr(params), ptr(gears), ptr(u),
-                                          ptr(out["cost"]), ptr(out["status"]), ptr(out["x"]),
+                                          ptr(out["cost"]), ptr(out["status"]), ptr(out.get("x")),
                                           ctypes.c_void_p(stream.cuda_stream))
         _abi.check(rc, "hvp_evaluate_batch")
         return out
 
-    def evaluate(self, sys_idx, roles, params, gears, u) -> dict:
+    def evaluate(self, sys_idx, roles, params, gears, u, want_x: bool = True) -> dict:
         """Host-array form of :meth:`evaluate_device` (synchronous)."""
         import torch
 
@@ -275,7 +277,7 @@ class BatchSolver:
         B = len(np.asarray(roles).reshape(-1))
         out = self.evaluate_device(t(sys_idx, torch.int32), t(roles, torch.int32),
                                    t(params, torch.float64).reshape(B, -1), t(gears, torch.int8).reshape(B, self.N),
-                                   t(u, torch.float64).reshape(B, self.N))
+                                   t(u, torch.float64).reshape(B, self.N), want_x=want_x)
         torch.cuda.synchronize(dev)
         return {k: v.cpu().numpy() for k, v in out.items()}
 

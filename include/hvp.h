@@ -245,7 +245,13 @@ int hvp_admm_update(hvp_handle* h, int P, int n, const double* x, const double* 
  * the label of the region the velocity lies in), u_in[B][N] = the control (u_g for the gear
  * model).  cost_out = objective of the resulting trajectory with optimal slacks, status_out =
  * HVP_OPTIMAL or HVP_INFEASIBLE (a constraint of the MLD model is violated; the reference returns
- * the string 'inf').  x_out[B][2][N+1] (may be NULL) receives the trajectory. */
+ * the string 'inf'; cost_out is then 1e300).  x_out[B][2][N+1] (may be NULL) receives the
+ * trajectory.  The mode of step k is the first region carrying the label gear_in[k] whose closed
+ * velocity band holds v_k (in the 7-region model regions 3 and 4 share label 4); a step without
+ * such a region is infeasible and is rolled on through region 0, so x_out is the trajectory only
+ * up to that step.  Every row (band, input box, acceleration rows, state box) is judged widened
+ * by 1e-9 * (1 + |value|), value = the quantity the row bounds (v_k, u_k, v_{k+1} - v_k,
+ * v_{k+1}, p_{k+1}): a solver's optimum that sits on a bound to rounding is feasible. */
 int hvp_evaluate_batch(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, const double* params,
                        const int8_t* gear_in, const double* u_in, double* cost_out, int32_t* status_out,
                        double* x_out, void* stream);
@@ -284,7 +290,9 @@ int hvp_gadmm_solve(hvp_handle* h, int P, int n, int lo, int m, const int32_t* s
 int hvp_gadmm_update(hvp_handle* h, int P, int n, int lo, int m, const double* x, const double* xf,
                      const double* xb, double* params, const int32_t* state, int init, void* stream);
 /* Sequence switching after an ADMM run (live platoons): seq_k moves across every edge flagged
- * in edge [B] into the region on the other side; sets state bit 2 when a sequence changed. */
+ * in edge [B] into the region on the other side; sets state bit 2 when a sequence changed.
+ * The lower edge wins when both bits of a step are set; an edge without a region on its other
+ * side (the state box) moves nothing; seq_0 never moves (edge has no bit for it). */
 int hvp_gadmm_switch(hvp_handle* h, int P, int n, int lo, int m, const int32_t* sys, const uint32_t* edge,
                      int8_t* seq, int32_t* state, void* stream);
 /* ---- Centralised MLD (mpcs/cent_mld.py MpcMldCent, fleet_cent_mld.py): replaces

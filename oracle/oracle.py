@@ -739,11 +739,13 @@ class GAdmmCoordinator:
         for k in range(1, self.N):
             r = int(sig[k])
             if (bits >> (2 * (k - 1))) & 1:  # lower edge of r active: into the region below
-                cand = [q for q in range(len(lo)) if q != r and abs(hi[q] - lo[r]) <= tol(lo[r])]
+                edge, other = lo[r], hi
             elif (bits >> (2 * (k - 1) + 1)) & 1:
-                cand = [q for q in range(len(lo)) if q != r and abs(lo[q] - hi[r]) <= tol(hi[r])]
+                edge, other = hi[r], lo
             else:
                 continue
+            # an unbounded band has no edge and so no neighbour (inf - inf <= inf would match any)
+            cand = [q for q in range(len(lo)) if q != r and np.isfinite(edge) and abs(other[q] - edge) <= tol(edge)]
             if cand:
                 out[k] = cand[0]
         return out
