@@ -1041,9 +1041,29 @@ HVP_HD inline int opaque_zero() {
     return z;
 }
 
-template <int N, class M>
+// Keeps a loaded value where it is: the compiler may neither sink the load behind it into a later
+// branch nor merge it with another load of the same address.
+template <class T>
+HVP_HD inline void pin_value(T& x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x));
+#else
+    (void)x;
+#endif
+}
+
+// BATCH (the refill kernels' event only): the lane's whole parameter row -- x0 and the 6 (N + 1)
+// doubles of x_front, x_back and leader_x -- is loaded up front, whatever the lane's role, and
+// pinned, so the row arrives as one run of wide loads behind one wait instead of one global-memory
+// round trip per role branch and step (the role tests below stay divergent branches, and without
+// the pins the compiler sinks each slice's load back into its branch).  The blocks a role does not
+// use are loaded and never read.  side / side_val: one more 8-byte word fetched with the row (the
+// event's incumbent key), pinned after the row so that it costs no wait of its own.
+// The arithmetic is the same expressions in the same order either way.
+template <int N, bool BATCH = false, class M>
 HVP_HD inline double direct_cost(const LaneQp<N, M>& q, const hvp_system& S_in, const Consts& C, int role,
-                                 const double* prm_in, uint64_t code, int K = N) {
+                                 const double* prm_in, uint64_t code, int K = N,
+                                 const unsigned long long* side = nullptr, unsigned long long* side_val = nullptr) {
 #if HVP_DC_OPAQUE_PTR
     const double* prm = opaque_ptr(prm_in);
     const hvp_system& S = *opaque_ptr(&S_in);
@@ -1052,6 +1072,21 @@ HVP_HD inline double direct_cost(const LaneQp<N, M>& q, const hvp_system& S_in, 
     const double* prm = reinterpret_cast<const double*>(reinterpret_cast<const char*>(prm_in) + z);
     const hvp_system& S = *reinterpret_cast<const hvp_system*>(reinterpret_cast<const char*>(&S_in) + z);
 #endif
+    constexpr int kRow = 2 + 6 * (N + 1);
+    double row[BATCH ? kRow : 1];
+    if constexpr (BATCH) {
+        unsigned long long sv = 0;
+        if (side) sv = *side;
+#pragma unroll
+        for (int j = 0; j < kRow; ++j) row[j] = prm[j];
+#pragma unroll
+        for (int j = 0; j < kRow; ++j) pin_value(row[j]);
+        if (side) {
+            pin_value(sv);
+            *side_val = sv;
+        }
+        prm = row;
+    }
     const double* xf = prm + 2;
     const double* xb = prm + 2 + 2 * (N + 1);
     const double* xl = prm + 2 + 4 * (N + 1);

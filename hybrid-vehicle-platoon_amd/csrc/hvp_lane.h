@@ -2636,6 +2636,44 @@ __device__ inline bool setup_node(Q& q, const hvp_system& S, const hvp::Consts& 
     return ok;
 }
 
+// setup_node for the refill event, its loads issued together: the instance's system index, role
+// and x0 first, the ws.iq row behind them, and one wait for all (setup_node's caller waits for
+// sys[inst] to address the table, then for the role and x0, before the row is asked for).
+template <int N, class Q>
+__device__ inline bool setup_node_batch(Q& q, const hvp_system* tab, const int32_t* sys, const int32_t* role,
+                                        const double* params, const hvp::Consts& C, const Workspace& ws, int inst,
+                                        uint64_t code, int K, double rlo, double rhi, unsigned* kmask) {
+    constexpr int NT = N * (N + 1) / 2;
+    const double* o = static_cast<const double*>(__builtin_assume_aligned(ws.iq + (size_t)inst * kIqStride<N>, 128));
+    const double* prm = params + (size_t)inst * C.stride;
+    int si = sys[inst], rl = role[inst];
+    double p0 = prm[0], v0 = prm[1];
+    double hf[N > 1 ? N - 1 : 1], hb[N > 1 ? N - 1 : 1];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) q.H[j] = o[j];
+#pragma unroll
+    for (int j = 0; j < N; ++j) q.f[j] = o[NT + j];
+#pragma unroll
+    for (int j = 0; j < N - 1; ++j) {
+        hf[j] = o[NT + N + j];
+        hb[j] = o[NT + 2 * N - 1 + j];
+    }
+    hvp::pin_value(si);
+    hvp::pin_value(rl);
+    hvp::pin_value(p0);
+    hvp::pin_value(v0);
+    const hvp_system& S = tab[si];
+    const bool ok = hvp::setup_scalars<N>(q, S, rl, p0, v0);
+#pragma unroll
+    for (int j = 0; j < N - 1; ++j) {
+        q.mem.set(hvp::F_HF, j, hf[j]);
+        q.mem.set(hvp::F_HB, j, hb[j]);
+    }
+    q.C0 = 0.0;
+    hvp::setup_input<N>(q, S, C, code, K, rlo, rhi, kmask);
+    return ok;
+}
+
 template <int N>
 __device__ inline void bnb_node_done(int k, long long t, int inst, bool ok, int its, double c, const double* y,
                                      const hvp::Consts& C, const Workspace& ws) {
@@ -2981,6 +3019,25 @@ __device__ inline const T* uniform_opaque(const T* p) {
 #ifndef HVP_REFILL_CHILD_ONCE
 #define HVP_REFILL_CHILD_ONCE 1
 #endif
+// The event's loads, batched (each 0: the code before, A/B):
+// HVP_REFILL_DC_BATCH: direct_cost loads the lane's whole parameter row before its step loop
+// (hvp_ipm.h, BATCH), for horizons up to kRefillDcBatchMaxN.
+// HVP_REFILL_INC_BATCH: the incumbent's key is fetched with that row instead of after the node's
+// write-back (needs DC_BATCH).
+// HVP_REFILL_NODE_BATCH: the claimed slot's four node fields are loaded together, then sys, role
+// and x0 together, instead of one after the other.
+#ifndef HVP_REFILL_DC_BATCH
+#define HVP_REFILL_DC_BATCH 1
+#endif
+#ifndef HVP_REFILL_INC_BATCH
+#define HVP_REFILL_INC_BATCH 1
+#endif
+#ifndef HVP_REFILL_NODE_BATCH
+#define HVP_REFILL_NODE_BATCH 1
+#endif
+constexpr int kRefillDcBatchMaxN = 8;
+template <int N>
+constexpr bool kRefillDcBatch = HVP_REFILL_DC_BATCH && N <= kRefillDcBatchMaxN;
 constexpr int kRefillSysCap = 8;
 #if HVP_REFILL_BYVAL
 // (round 3's kernel body: the descriptor and the constants as by-value kernel arguments, the
@@ -3059,8 +3116,14 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
             } else if (done) {
                 const int st = stage == RS_OPT ? g.verify(C, nullptr) : fail;
                 const bool ok = st == hvp::GI_OK;
-                const double c = ok ? hvp::direct_cost<N>(q, tab[sys[inst]], C, role[inst],
-                                                          params + (size_t)inst * C.stride, code, k)
+                // the incumbent's key, fetched with the cost's row (only leaves move it, and a launch
+                // of level k < N runs none; at k == N it is not read)
+                constexpr bool kInc = kRefillDcBatch<N> && HVP_REFILL_INC_BATCH;
+                unsigned long long inck = 0;
+                if (kInc && !ok) inck = ws.inc[inst];
+                const double c = ok ? hvp::direct_cost<N, kRefillDcBatch<N>>(
+                                          q, tab[sys[inst]], C, role[inst], params + (size_t)inst * C.stride, code,
+                                          k, kInc ? ws.inc + inst : nullptr, &inck)
                                     : 0.0;
                 iter_sum += (unsigned long long)g.iter;
                 csteps = ok ? g.iter : -1;
@@ -3076,7 +3139,8 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
                 // the incumbent only changes at the leaves (level N): below N this pruning test
                 // sees the value a separate expand kernel would
                 clb = ok ? c : -1e300;
-                if (k < N && !(ws.inst_flag[inst] & 2) && !hvp::bnb_pruned(clb, inc_of(ws, inst))) {
+                if (k < N && !(ws.inst_flag[inst] & 2) &&
+                    !hvp::bnb_pruned(clb, kInc ? key_cost(inck) : inc_of(ws, inst))) {
 #if HVP_REFILL_CHILD_ONCE
                     cmask = nmask;
 #else
@@ -3113,21 +3177,43 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
                 const long long mc = (long long)base + wave_rank(free);
                 const long long mine = lvl.slot(mc);
                 if (stage == RS_IDLE && mc < total) {
+#if HVP_REFILL_NODE_BATCH
+                    // the slot's four fields together (a dead slot's other three are allocated
+                    // and not looked at)
+                    int ninst = ws.nd_inst[dst][mine];
+                    uint64_t ncode = ws.nd_code[dst][mine];
+                    double nlo = ws.nd_lo[dst][mine], nhi = ws.nd_hi[dst][mine];
+                    hvp::pin_value(ninst);
+                    hvp::pin_value(ncode);
+                    hvp::pin_value(nlo);
+                    hvp::pin_value(nhi);
+                    inst = ninst;
+#else
                     inst = ws.nd_inst[dst][mine];
+#endif
                     if (inst < 0) {  // dead slot of an overflowed reservation
                         if (k == N) ws.leaf_stat[mine] = HVP_OVERFLOW;
                         else ws.nd_lb[dst][mine] = 1e300;
                     } else {
                         t = mine;
+#if HVP_REFILL_NODE_BATCH
+                        code = ncode;
+#else
                         code = ws.nd_code[dst][mine];
+#endif
                         if (code & kPassFlag) {  // its parent's QP: finished at the next event
                             fail = (int)((code >> 56) & 127);
                             code &= kPassCode;
                             stage = RS_PASS;
                         } else {
+#if HVP_REFILL_NODE_BATCH
+                            setup_node_batch<N>(q, tab, sys, role, params, C, ws, inst, code, k, nlo, nhi,
+                                                HVP_REFILL_CHILD_ONCE ? &nmask : nullptr);
+#else
                             setup_node<N>(q, tab[sys[inst]], C, ws, inst, role[inst],
                                           params + (size_t)inst * C.stride, code, k, ws.nd_lo[dst][mine],
                                           ws.nd_hi[dst][mine], HVP_REFILL_CHILD_ONCE ? &nmask : nullptr);
+#endif
                             stage = g.init(q) == hvp::GI_OK ? RS_SCAN : RS_FAIL;
                             fail = hvp::GI_FAIL_CHOL;
                         }
