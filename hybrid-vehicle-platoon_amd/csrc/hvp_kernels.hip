@@ -665,9 +665,12 @@ int hvp_get_stats(hvp_handle* h, hvp_stats* out) {
         const unsigned long long* pf = lv2 + 2 * (HVP_MAX_N + 1) - 8;
         std::fprintf(stderr,
                      "[refill-prof] event cycles %llu of %llu (%.3f), wave trips %llu, busy lane-trips %llu (%.3f); "
-                     "write-back %llu (until cost %llu, until children %llu), claim %llu\n",
+                     "write-back %llu (until cost %llu, until children %llu), claim %llu; scan %llu (%.3f), "
+                     "step %llu (%.3f)\n",
                      pf[0], pf[1], pf[1] ? (double)pf[0] / (double)pf[1] : 0.0, pf[3], pf[2],
-                     pf[3] ? (double)pf[2] / (64.0 * (double)pf[3]) : 0.0, pf[4], pf[6], pf[7], pf[5]);
+                     pf[3] ? (double)pf[2] / (64.0 * (double)pf[3]) : 0.0, pf[4], pf[6], pf[7], pf[5], pf[-2],
+                     pf[1] ? (double)pf[-2] / (double)pf[1] : 0.0, pf[-1],
+                     pf[1] ? (double)pf[-1] / (double)pf[1] : 0.0);
     }
 #endif
     out->capacity = h->ws.cap;

@@ -2969,15 +2969,29 @@ enum { RS_IDLE = 0, RS_SCAN = 1, RS_STEP = 2, RS_FAIL = 3, RS_OPT = 4, RS_PASS =
 
 // one active-set trip of a busy lane (RS_SCAN / RS_STEP); finished lanes end in RS_FAIL / RS_OPT
 template <int N, class Q>
-__device__ inline void gi_trip(Q& q, hvp::GiLane<N>& g, const hvp::Consts& C, int& stage, int& fail) {
+__device__ inline void gi_trip(Q& q, hvp::GiLane<N>& g, const hvp::Consts& C, int& stage, int& fail
+#ifdef HVP_REFILL_PROF  // diagnostics build: the wave's cycles in the scan and in the step
+                        , unsigned long long* pf_scan = nullptr, unsigned long long* pf_step = nullptr
+#endif
+) {
     q.mem.refresh();
     g.fence(q);
+#ifdef HVP_REFILL_PROF
+    const unsigned long long pf_s0 = __builtin_amdgcn_s_memtime();
+#endif
     if (stage == RS_SCAN) stage = g.scan(q, C) ? RS_STEP : RS_OPT;
+#ifdef HVP_REFILL_PROF
+    const unsigned long long pf_s1 = __builtin_amdgcn_s_memtime();
+    if (pf_scan) *pf_scan += pf_s1 - pf_s0;
+#endif
     if (stage == RS_STEP) {
         const int r = g.step(q, C, kGiMaxIter<N>);
         if (r == hvp::GI_STEP_NEXT) stage = RS_SCAN;
         else if (r != hvp::GI_STEP_MORE) stage = RS_FAIL, fail = r;
     }
+#ifdef HVP_REFILL_PROF
+    if (pf_step) *pf_step += __builtin_amdgcn_s_memtime() - pf_s1;
+#endif
 }
 
 #ifdef HVP_REFILL_PROF
@@ -3039,16 +3053,84 @@ constexpr int kRefillDcBatchMaxN = 8;
 template <int N>
 constexpr bool kRefillDcBatch = HVP_REFILL_DC_BATCH && N <= kRefillDcBatchMaxN;
 constexpr int kRefillSysCap = 8;
+// The block's copy of what is uniform over a launch and holds no pointer: the problem constants
+// (~95 dwords with dec[16] and acc[16]) and the hoisted level list, written to LDS once at entry
+// (before the one barrier) and read from there.  Together with the workspace descriptor's ~120
+// dwords the kernel arguments, live across the persistent loop, are twice the 102 SGPRs: the rest
+// sits in VGPR lanes (v_writelane / v_readlane, one dword at a time, 84 of them in the trip's
+// scan for C.dec[j], C.acc[j], C.w and the tolerances) and pushes lane state into scratch.  The
+// readers bind references to the __shared__ object itself, so the address space stays known after
+// inlining (ds_read, never flat_load), and LDS reads cannot alias the event's global stores.
+// uni_view() makes the object's offset opaque where it is called -- once per event, once per
+// trip -- so the loads stay there instead of being hoisted above the loop into registers again
+// (as LdsMem::refresh() does for the lane rows).
+// The descriptor itself stays a by-value argument: a pointer read back from LDS is a generic one
+// to the compiler (flat_load / flat_store / flat_atomic for every access of the event -- a cast
+// through the global address space is folded away, and a local copy with the casts is indexed by
+// the level's parity at run time, so it lands in scratch), where a kernel argument is known to
+// point to global memory.
+// HVP_REFILL_UNI_LDS: master switch; HVP_REFILL_UNI_EVENT: the event's reads (constants, level
+// list); HVP_REFILL_UNI_TRIP: the trips' Consts reads.  0: the by-value arguments, the code
+// before (A/B).  The trips keep the argument (default 0): with the event off it, the constants
+// the scan needs fit the scalar registers, and uniform values read from LDS land in VGPRs, which
+// the trip has none to spare (measured: event alone -5.1 %, both -4.0 %, trips alone -1.6 %,
+// profiles/r08a_refill_uniform_ab.jsonl).
+// HVP_REFILL_CLAIM_EARLY: the claim's atomic is issued at the top of the event (the free lanes
+// are known there, and whether the list is exhausted does not depend on the write-back) and
+// consumed after the write-back.  Claim order only decides which wave solves which node.
+#ifndef HVP_REFILL_UNI_LDS
+#define HVP_REFILL_UNI_LDS 1
+#endif
+#ifndef HVP_REFILL_UNI_TRIP
+#define HVP_REFILL_UNI_TRIP 0
+#endif
+#ifndef HVP_REFILL_UNI_EVENT
+#define HVP_REFILL_UNI_EVENT 1
+#endif
+#ifndef HVP_REFILL_CLAIM_EARLY
+#define HVP_REFILL_CLAIM_EARLY 0
+#endif
+// The event reads the copy at the horizons where that takes the kernel off scratch (N >= 5: every
+// one of them holds less scratch per lane with it, profiles/r08a_refill_static.txt).  Below, the
+// arguments fit the registers, the copy only costs a few (N = 2: 162 -> 171 VGPRs, N = 2 and 4:
+// 36 B/lane of scratch that the code before does not have), and those horizons keep that code.
+constexpr int kRefillUniMinN = 5;
+template <int N>
+constexpr bool kRefillUniEvent = HVP_REFILL_UNI_LDS && HVP_REFILL_UNI_EVENT && N >= kRefillUniMinN;
+template <int N>
+constexpr bool kRefillUniFill = HVP_REFILL_UNI_LDS && (kRefillUniEvent<N> || HVP_REFILL_UNI_TRIP);
+struct RefillUni {
+    hvp::Consts C;
+    LevelList lvl;
+    long long total;  // lvl.count()
+};
+static_assert(sizeof(RefillUni) <= 4096 - 64, "N = 5: rows 71,680 B + tables 6,144 B + this <= 81,920 B (2 blocks per CU)");
+template <class T>
+__device__ inline const T& uni_view(const T& obj) {
+    unsigned off = 0;
+    asm volatile("" : "+s"(off));
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(&obj) + off);
+}
 #if HVP_REFILL_BYVAL
 // (round 3's kernel body: the descriptor and the constants as by-value kernel arguments, the
 // level list hoisted)
 template <int N, bool STAGE>
 __global__ __launch_bounds__(kBnbBlock<N>) __attribute__((amdgpu_waves_per_eu(HVP_REFILL_WAVES)))
 void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys, const int32_t* __restrict__ sys,
-                        const int32_t* __restrict__ role, const double* __restrict__ params, hvp::Consts C,
-                        Workspace ws) {
+                        const int32_t* __restrict__ role, const double* __restrict__ params, hvp::Consts C_arg,
+                        Workspace ws_arg) {
     constexpr int BS = kBnbBlock<N>;
     static_assert(N <= HVP_MAX_N_ENUM, "lane refill is the N <= 8 path");
+    constexpr bool kUniEvent = kRefillUniEvent<N>;
+    __shared__ RefillUni s_uni;  // (takes no LDS where nothing below uses it)
+    const RefillUni& U = s_uni;
+    if constexpr (kRefillUniFill<N>) {
+        if (threadIdx.x == 0) {  // (from the arguments' scalar registers; the barrier is below)
+            s_uni.C = C_arg;
+            s_uni.lvl = level_list(ws_arg, k);
+            s_uni.total = s_uni.lvl.count();
+        }
+    }
     const hvp_system* tab = systems;  // the tables the event reads
     if constexpr (STAGE) {
         __shared__ hvp_system s_sys[kRefillSysCap];
@@ -3058,13 +3140,14 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
         unsigned long long* dstw = reinterpret_cast<unsigned long long*>(s_sys);
         const int nw = (n_sys < kRefillSysCap ? n_sys : kRefillSysCap) * kWords;
         for (int i = threadIdx.x; i < nw; i += BS) dstw[i] = src[i];
-        __syncthreads();
         tab = s_sys;
     }
+    if (STAGE || kRefillUniFill<N>) __syncthreads();  // the only barrier: waves leave the loop at different times
     const int dst = k & 1;
-    const LevelList lvl = level_list(ws, k);
-    const long long total = lvl.count();
-    unsigned long long* claim = ws.lvl + (HVP_MAX_N + 1) + k;
+    const Workspace& ws = ws_arg;
+    const LevelList lvl_arg = level_list(ws, k);  // (the code before; unused where the event reads the copy)
+    const long long total_arg = lvl_arg.count();
+    unsigned long long* const claim_arg = ws.lvl + (HVP_MAX_N + 1) + k;
     const int lane = threadIdx.x & 63;
     hvp::LaneQp<N, LdsMem<N, BS>> q;
     q.mem.lane = threadIdx.x;
@@ -3077,6 +3160,7 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
     unsigned long long iter_sum = 0, pass_n = 0;
 #ifdef HVP_REFILL_PROF  // diagnostics build: event / trip cycles and busy lane-trips per wave
     unsigned long long pf_ev = 0, pf_all = 0, pf_busy = 0, pf_trips = 0, pf_wb = 0, pf_cl = 0, pf_dc = 0, pf_rs = 0;
+    unsigned long long pf_scan = 0, pf_step = 0;
     const unsigned long long pf_t0 = __builtin_amdgcn_s_memtime();
     int pf_mine = 0, pf_gen = 0;
 #endif
@@ -3085,21 +3169,35 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
         const unsigned long long free = __ballot(stage == RS_IDLE || done);
         const int nfree = __popcll(free);
 #ifdef HVP_REFILL_PROF
-        const unsigned long long pf_e0 = __builtin_amdgcn_s_memtime();
         const bool pf_event = nfree >= kRefillMin || nfree == 64;
         pf_busy += (unsigned long long)(64 - nfree);
         pf_trips += 1;
         if (pf_event) {
+            // (the histogram's atomics -- 64 lanes on a few shared words -- complete before the
+            // event's stamp, so they are charged to neither the event nor "until cost")
             if (done) atomicAdd(&g_pf_hist[pf_mine < 63 ? pf_mine : 63], 1ull);
             if (lane == 0) atomicAdd(&g_pf_hist[64 + (pf_gen < 63 ? pf_gen : 63)], 1ull);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             pf_gen = 0;
             pf_mine = 0;
         }
         ++pf_gen;
         if (stage == RS_SCAN || stage == RS_STEP) ++pf_mine;
+        const unsigned long long pf_e0 = __builtin_amdgcn_s_memtime();
 #endif
         if (nfree >= kRefillMin || nfree == 64) {
             // ---- event: write the finished lanes' results, then refill every free lane
+            const RefillUni* E = nullptr;
+            if constexpr (kUniEvent) E = &uni_view(U);
+            const hvp::Consts& C = kUniEvent ? E->C : C_arg;
+            const LevelList& lvl = kUniEvent ? E->lvl : lvl_arg;
+            const long long total = kUniEvent ? E->total : total_arg;
+            unsigned long long* const claim = kUniEvent ? ws.lvl + (HVP_MAX_N + 1) + k : claim_arg;
+#if HVP_REFILL_CLAIM_EARLY
+            unsigned long long claimed = 0;  // (the leader's lane holds the claim's first item)
+            if (!exhausted && lane == __ffsll((long long)free) - 1)
+                claimed = atomicAdd(claim, (unsigned long long)nfree);
+#endif
             unsigned cmask = 0;  // children of a finished bound node (k_bnb_expand's work, fused)
             double clb = 0.0;
             int csteps = 0;      // the finished node's active-set steps (its children's bucket)
@@ -3165,7 +3263,14 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
             pf_wb += pf_w1 - pf_e0;
 #endif
             if (!exhausted) {
+#if HVP_REFILL_CLAIM_EARLY
+                const int leader = __ffsll((long long)free) - 1;
+                const unsigned long long base =
+                    ((unsigned long long)(unsigned)__shfl((int)(claimed >> 32), leader, 64) << 32) |
+                    (unsigned)__shfl((int)(claimed & 0xffffffffu), leader, 64);
+#else
                 const unsigned long long base = wave_claim(claim, free, nfree, lane);
+#endif
 #ifdef HVP_REFILL_PROF
                 {
                     const unsigned long long bb = __builtin_amdgcn_readfirstlane((unsigned)base);
@@ -3224,7 +3329,18 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
 #ifdef HVP_REFILL_PROF
         if (pf_event) pf_ev += __builtin_amdgcn_s_memtime() - pf_e0;
 #endif
-        if (stage == RS_SCAN || stage == RS_STEP) gi_trip<N>(q, g, C, stage, fail);
+        if (stage == RS_SCAN || stage == RS_STEP) {
+#if HVP_REFILL_UNI_LDS && HVP_REFILL_UNI_TRIP
+            const hvp::Consts& Ct = uni_view(U.C);
+#else
+            const hvp::Consts& Ct = C_arg;
+#endif
+#ifdef HVP_REFILL_PROF
+            gi_trip<N>(q, g, Ct, stage, fail, &pf_scan, &pf_step);
+#else
+            gi_trip<N>(q, g, Ct, stage, fail);
+#endif
+        }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -3235,8 +3351,10 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
     if (lane == 0 && pass_n) atomicAdd(&ws.counter[6], pass_n);  // pass-through nodes (no QP; hvp_get_stats)
 #ifdef HVP_REFILL_PROF
     pf_all = __builtin_amdgcn_s_memtime() - pf_t0;
-    if (lane == 0) {  // the claim slots of levels > N are free (prof builds need N <= 8)
+    if (lane == 0) {  // the claim slots of levels > N are free (prof builds need N <= 6)
         unsigned long long* pf = ws.lvl + 2 * (HVP_MAX_N + 1) - 8;
+        atomicAdd(&pf[-2], pf_scan);
+        atomicAdd(&pf[-1], pf_step);
         atomicAdd(&pf[0], pf_ev);
         atomicAdd(&pf[1], pf_all);
         atomicAdd(&pf[2], pf_busy);
