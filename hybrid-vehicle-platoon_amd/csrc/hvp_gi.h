@@ -108,16 +108,57 @@ struct GiMask<N, true> {
 // its reversed copy (violated when the row is satisfied strictly).  The chosen row's bound d
 // and U-row coefficient a are returned with it (d_out, a_out), so that the active-set steps
 // build the row from registers (gi_normal) without indexing the per-lane rows dynamically.
-template <int N, class M>
+//
+// A/B switches of the scan (0 = the code before; every setting decides exactly the same row):
+//   HVP_GI_SCAN_FIRST  the selection test without its `best < 0` half (see consider below)
+//   HVP_GI_SCAN_GUARD  a group of rows is only looked at when one of them lies outside its bound
+//                      (a whole wave whose lanes all satisfy the group branches over it).  Bit 0:
+//                      the six V/U/A rows of a step; bit 1: its four prefix rows; bit 2: the two
+//                      position-box rows among them.  Measured at the flagship shape (DESIGN.md
+//                      section 4): no wave ever selects at a box row and that guard wins; the
+//                      other two groups hold a violating lane in most scans and their guards
+//                      lose, so only bit 2 ships.
+//   HVP_GI_SCAN_GUARD_MAX_N  the guards apply up to this horizon: at N = 8, where the kernels
+//                      spill, the box-row guard is behind the unguarded scan.
+#ifndef HVP_GI_SCAN_FIRST
+#define HVP_GI_SCAN_FIRST 1
+#endif
+#ifndef HVP_GI_SCAN_GUARD
+#define HVP_GI_SCAN_GUARD 4
+#endif
+#ifndef HVP_GI_SCAN_GUARD_MAX_N
+#define HVP_GI_SCAN_GUARD_MAX_N 5
+#endif
+
+// Diagnostics hook of the scan: called once per row, by every scanning lane, with whether the lane
+// violates the row (hvp_lane.h counts the waves that do in its HVP_REFILL_PROF build).
+struct GiNoProbe {
+    HVP_HD void operator()(int, bool) const {}
+};
+
+template <int N, class M, class Probe = GiNoProbe>
 HVP_HD inline int gi_most_violated(const LaneQp<N, M>& q, const Consts& C, const double* y, const GiMask<N>& act,
-                                   uint32_t sat, double tol, double& d_out, double& a_out) {
+                                   uint32_t sat, double tol, double& d_out, double& a_out, Probe probe = Probe()) {
+    constexpr int kGuard = N <= HVP_GI_SCAN_GUARD_MAX_N ? HVP_GI_SCAN_GUARD : 0;
     int best = -1;
+    // (0, 1): the first candidate wins against them by the comparison itself, see below
     double best_v2 = 0.0, best_nn = 1.0, best_d = 0.0, best_a = 0.0;
     auto consider = [&](int id, double slack, double nn, double scale, double d, double a) {
-        if (act.get(id & (GI_REV - 1)) || !(slack < -tol * scale)) return;
+        const bool viol = !act.get(id & (GI_REV - 1)) && slack < -tol * scale;
+        probe(id & (GI_REV - 1), viol);
+        if (!viol) return;
         // maximise slack^2 / |c|^2 among violated rows
         const double v2 = slack * slack;
+#if HVP_GI_SCAN_FIRST
+        // No `best < 0 ||` in front: while best < 0, (best_v2, best_nn) = (0, 1), and a row gets
+        // here only with slack < -tol * scale <= -tol (scale >= 1, tol = 1e-11), so v2 > 0 (no
+        // underflow: v2 > 1e-22; an overflow gives +inf); nn is finite (1, 2, 1 + a^2 or a
+        // multiple of ts^2), so best_v2 * nn = 0 and v2 * 1 > 0 holds by itself.  For every later
+        // candidate best >= 0 already.
+        if (v2 * best_nn > best_v2 * nn) {
+#else
         if (best < 0 || v2 * best_nn > best_v2 * nn) {
+#endif
             best = id;
             best_v2 = v2;
             best_nn = nn;
@@ -136,25 +177,37 @@ HVP_HD inline int gi_most_violated(const LaneQp<N, M>& q, const Consts& C, const
         const double vl = q.vlo(j), vh = q.vhi(j), ul = q.ulo(j), uh = q.uhi(j), al = C.dec[j], ah = C.acc[j];
         // row bounds in <= form (gi_row): the step-1 rows carry the constant -a v0 / -v0
         const double cu = j == 0 ? -a * q.v0 : 0.0, ca = j == 0 ? -q.v0 : 0.0;
-        consider(6 * j + 0, gv - vl, 1.0, 1.0 + fabs(vl), -vl, a);
-        consider(6 * j + 1, vh - gv, 1.0, 1.0 + fabs(vh), vh, a);
-        consider(6 * j + 2, gu - ul, nu, 1.0 + fabs(ul) + fabs(a * yprev), cu - ul, a);
-        consider(6 * j + 3, uh - gu, nu, 1.0 + fabs(uh) + fabs(a * yprev), uh - cu, a);
-        consider(6 * j + 4, ga - al, na, 1.0 + fabs(yprev), ca - al, a);
-        consider(6 * j + 5, ah - ga, na, 1.0 + fabs(yprev), ah - ca, a);
+        // Guards (HVP_GI_SCAN_GUARD): a row is a candidate only with slack < -tol * scale < 0, and
+        // for finite operands the difference x - b is negative exactly when x < b (IEEE
+        // subtraction with gradual underflow never rounds a non-zero difference to zero), so a
+        // group none of whose row values lies outside its bound holds no candidate.
+        if (!(kGuard & 1) || gv < vl || gv > vh || gu < ul || gu > uh || ga < al || ga > ah) {
+            consider(6 * j + 0, gv - vl, 1.0, 1.0 + fabs(vl), -vl, a);
+            consider(6 * j + 1, vh - gv, 1.0, 1.0 + fabs(vh), vh, a);
+            consider(6 * j + 2, gu - ul, nu, 1.0 + fabs(ul) + fabs(a * yprev), cu - ul, a);
+            consider(6 * j + 3, uh - gu, nu, 1.0 + fabs(uh) + fabs(a * yprev), uh - cu, a);
+            consider(6 * j + 4, ga - al, na, 1.0 + fabs(yprev), ca - al, a);
+            consider(6 * j + 5, ah - ga, na, 1.0 + fabs(yprev), ah - ca, a);
+        }
         if (k >= 2) {
             const int m = k - 2;
             cum += y[m];
             const double p = q.P1 + q.ts * cum, nn = q.ts * q.ts * (m + 1);
             const double sc = 1.0 + fabs(p);
             const int b = 6 * N + 4 * m;
-            consider(b + 0, p - q.pmin, nn, sc, q.P1 - q.pmin, a);
-            consider(b + 1, q.pmax - p, nn, sc, q.pmax - q.P1, a);
             const double hf = q.hf(m), hb = q.hb(m);
-            const double sfw = hf - p, sbw = p - hb;
             const bool satf = (sat >> (2 * m)) & 1u, satb = (sat >> (2 * m + 1)) & 1u;
-            consider(satf ? (b + 2) | GI_REV : b + 2, satf ? -sfw : sfw, nn, sc, satf ? q.P1 - hf : hf - q.P1, a);
-            consider(satb ? (b + 3) | GI_REV : b + 3, satb ? -sbw : sbw, nn, sc, satb ? hb - q.P1 : q.P1 - hb, a);
+            // (a saturated soft row stands reversed: violated when strictly satisfied)
+            if (!(kGuard & 2) || p < q.pmin || p > q.pmax || (satf ? p < hf : p > hf) ||
+                (satb ? p > hb : p < hb)) {
+                if (!(kGuard & 4) || p < q.pmin || p > q.pmax) {
+                    consider(b + 0, p - q.pmin, nn, sc, q.P1 - q.pmin, a);
+                    consider(b + 1, q.pmax - p, nn, sc, q.pmax - q.P1, a);
+                }
+                const double sfw = hf - p, sbw = p - hb;
+                consider(satf ? (b + 2) | GI_REV : b + 2, satf ? -sfw : sfw, nn, sc, satf ? q.P1 - hf : hf - q.P1, a);
+                consider(satb ? (b + 3) | GI_REV : b + 3, satb ? -sbw : sbw, nn, sc, satb ? hb - q.P1 : q.P1 - hb, a);
+            }
         }
         yprev = yk;
     }
@@ -296,9 +349,9 @@ struct GiLane {
     }
 
     // step 1: the most violated row becomes p; false when the point is feasible (optimal)
-    template <class M>
-    HVP_HD bool scan(const LaneQp<N, M>& q, const Consts& C) {
-        p = gi_most_violated(q, C, q.y, act, sat, 1e-11, pd, pa);
+    template <class M, class Probe = GiNoProbe>
+    HVP_HD bool scan(const LaneQp<N, M>& q, const Consts& C, Probe probe = Probe()) {
+        p = gi_most_violated(q, C, q.y, act, sat, 1e-11, pd, pa, probe);
         unew = 0.0;
         return p >= 0;
     }

@@ -685,9 +685,55 @@ void gadmm_one(const hvp_system& S, const hvp::Consts& C, int role, const double
     }
 }
 
+// hvp_hostref_gi_scan for one horizon.  Lane data layout (doubles): the per-step rows
+// [F_COUNT][N] (hvp_ipm.h F_AM .. F_HB, field-major), then v0, P1, ts, pmin, pmax, then
+// dec[N], acc[N].
+template <int N>
+void gi_scan_one(const hvp_system& S, hvp::Consts C, int role, const double* prm, uint64_t code, int K, double lo,
+                 double hi, const double* y, const int32_t* active, int nactive, uint32_t sat, const double* data_in,
+                 double* data_out, int32_t* id, double* d, double* a) {
+    hvp::LaneQp<N> q;
+    hvp::setup_lane<N>(q, S, C, role, prm, code, K, lo, hi);
+    constexpr int NR = hvp::F_COUNT * N;
+    if (data_in) {
+        for (int i = 0; i < NR; ++i) q.mem.set(i / N, i % N, data_in[i]);
+        q.v0 = data_in[NR], q.P1 = data_in[NR + 1], q.ts = data_in[NR + 2];
+        q.pmin = data_in[NR + 3], q.pmax = data_in[NR + 4];
+        for (int j = 0; j < N; ++j) C.dec[j] = data_in[NR + 5 + j], C.acc[j] = data_in[NR + 5 + N + j];
+    }
+    if (data_out) {
+        for (int i = 0; i < NR; ++i) data_out[i] = q.mem.get(i / N, i % N);
+        data_out[NR] = q.v0, data_out[NR + 1] = q.P1, data_out[NR + 2] = q.ts;
+        data_out[NR + 3] = q.pmin, data_out[NR + 4] = q.pmax;
+        for (int j = 0; j < N; ++j) data_out[NR + 5 + j] = C.dec[j], data_out[NR + 5 + N + j] = C.acc[j];
+    }
+    hvp::GiMask<N> act;
+    for (int i = 0; i < nactive; ++i) act.set(active[i], true);
+    *id = hvp::gi_most_violated<N>(q, C, y, act, sat, 1e-11, *d, *a);
+}
+
 }  // namespace
 
 extern "C" {
+
+// The active-set scan alone (hvp_gi.h gi_most_violated; test use only): the lane QP of (problem,
+// system, role, parameter row, region code, K, interval), optionally with its row data replaced
+// (data_in, layout at gi_scan_one; data_out returns what the scan read), scanned at y with the
+// given active row ids and saturation bits.  Returns the chosen id (-1: none) with d and a.
+int hvp_hostref_gi_scan(const hvp_problem* P, const hvp_system* S, int role, const double* prm,
+                        unsigned long long code, int K, double lo, double hi, const double* y, const int32_t* active,
+                        int nactive, uint32_t sat, const double* data_in, double* data_out, int32_t* id, double* d,
+                        double* a) {
+    const hvp::Consts C = make_consts(*P);
+    switch (P->N) {
+#define HVP_CASE(n) \
+    case n: gi_scan_one<n>(*S, C, role, prm, code, K, lo, hi, y, active, nactive, sat, data_in, data_out, id, d, a); break;
+        HVP_CASE(2) HVP_CASE(3) HVP_CASE(4) HVP_CASE(5) HVP_CASE(6) HVP_CASE(7) HVP_CASE(8)
+#undef HVP_CASE
+        default: return HVP_E_UNSUPPORTED;
+    }
+    return 0;
+}
 
 // HVP_FORM_GADMM local QPs for given sequences (test use only): the lane algorithm on the host.
 int hvp_hostref_gadmm_solve(const hvp_problem* P, const hvp_system* systems, int B, const int32_t* sys,

@@ -2967,10 +2967,48 @@ __global__ __launch_bounds__(kBnbBlock<N>) HVP_LP_OCC void k_lp_bound_refill(int
 // RS_PASS: a pass-through node (bnb_put_children kPassFlag), finished without a QP
 enum { RS_IDLE = 0, RS_SCAN = 1, RS_STEP = 2, RS_FAIL = 3, RS_OPT = 4, RS_PASS = 5 };
 
+#ifdef HVP_REFILL_PROF
+// Switches of the diagnostics build:
+//   HVP_REFILL_PROF_PIN   1: gi_trip's stamps wait for the code they close (see gi_trip); 0: the
+//                         bare stamps of the earlier rounds, for comparison
+//   HVP_REFILL_PROF_ROWS  1: per-row counts of the scan's selection blocks (their ballots and
+//                         atomics sit inside the scan: a build for the counts, not for the cycles)
+#ifndef HVP_REFILL_PROF_PIN
+#define HVP_REFILL_PROF_PIN 1
+#endif
+#ifndef HVP_REFILL_PROF_ROWS
+#define HVP_REFILL_PROF_ROWS 0
+#endif
+// [0, 64): busy trips per node; [64, 128): trips per generation (event to event);
+// [128, 128 + kPfRows): per row id of the scan, the scans (one per wave and trip) in which at
+// least one scanning lane violates the row, i.e. the wave runs the row's selection block;
+// [128 + kPfRows]: all scans (wave trips with a scanning lane)
+constexpr int kPfRows = 80;  // row ids of N <= 8 (at most 76)
+constexpr int kPfHist = 128 + kPfRows + 1;
+__device__ unsigned long long g_pf_hist[kPfHist];
+
+// the scan's diagnostics hook (hvp_gi.h gi_most_violated): one ballot per row over the lanes that
+// scan, counted by the first of them
+struct ScanProbe {
+    __device__ void operator()(int id, bool viol) const {
+        const unsigned long long any = __ballot(viol), me = __ballot(true);
+        const bool first = (int)(threadIdx.x & 63) == __ffsll((long long)me) - 1;
+        if (first && id == 0) atomicAdd(&g_pf_hist[128 + kPfRows], 1ull);
+        if (first && any) atomicAdd(&g_pf_hist[128 + id], 1ull);
+    }
+};
+#endif
+
 // one active-set trip of a busy lane (RS_SCAN / RS_STEP); finished lanes end in RS_FAIL / RS_OPT
+//
+// Diagnostics build: the wave's cycles in the scan and in the step.  A stamp is no barrier for
+// arithmetic: the scan and the step are register code, and the compiler is free to finish them
+// after the stamp that should close them.  With HVP_REFILL_PROF_PIN the values a half returns
+// pass through an empty asm before its closing stamp, so they are computed by then (measured:
+// it moves little, scan 0.029 -> 0.044 of a wave's life).
 template <int N, class Q>
 __device__ inline void gi_trip(Q& q, hvp::GiLane<N>& g, const hvp::Consts& C, int& stage, int& fail
-#ifdef HVP_REFILL_PROF  // diagnostics build: the wave's cycles in the scan and in the step
+#ifdef HVP_REFILL_PROF
                         , unsigned long long* pf_scan = nullptr, unsigned long long* pf_step = nullptr
 #endif
 ) {
@@ -2979,8 +3017,15 @@ __device__ inline void gi_trip(Q& q, hvp::GiLane<N>& g, const hvp::Consts& C, in
 #ifdef HVP_REFILL_PROF
     const unsigned long long pf_s0 = __builtin_amdgcn_s_memtime();
 #endif
+#if defined(HVP_REFILL_PROF) && HVP_REFILL_PROF_ROWS
+    if (stage == RS_SCAN) stage = g.scan(q, C, ScanProbe()) ? RS_STEP : RS_OPT;
+#else
     if (stage == RS_SCAN) stage = g.scan(q, C) ? RS_STEP : RS_OPT;
+#endif
 #ifdef HVP_REFILL_PROF
+#if HVP_REFILL_PROF_PIN
+    asm volatile("" : "+v"(g.p), "+v"(g.pd), "+v"(g.pa), "+v"(stage));
+#endif
     const unsigned long long pf_s1 = __builtin_amdgcn_s_memtime();
     if (pf_scan) *pf_scan += pf_s1 - pf_s0;
 #endif
@@ -2990,14 +3035,13 @@ __device__ inline void gi_trip(Q& q, hvp::GiLane<N>& g, const hvp::Consts& C, in
         else if (r != hvp::GI_STEP_MORE) stage = RS_FAIL, fail = r;
     }
 #ifdef HVP_REFILL_PROF
+#if HVP_REFILL_PROF_PIN
+    g.fence(q);
+    asm volatile("" : "+v"(g.unew), "+v"(g.nact), "+v"(stage), "+v"(fail));
+#endif
     if (pf_step) *pf_step += __builtin_amdgcn_s_memtime() - pf_s1;
 #endif
 }
-
-#ifdef HVP_REFILL_PROF
-// [0, 64): busy trips per node; [64, 128): trips per generation (event to event)
-__device__ unsigned long long g_pf_hist[128];
-#endif
 
 // A uniform pointer the compiler must treat as unknown at this point: loads through it cannot be
 // hoisted above it (k_bnb_bound_refill reads its event-only constants this way, so they occupy
@@ -3329,6 +3373,14 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
 #ifdef HVP_REFILL_PROF
         if (pf_event) pf_ev += __builtin_amdgcn_s_memtime() - pf_e0;
 #endif
+#ifdef HVP_REFILL_PROF
+        // (the trip's two stamps are the wave's, but only the busy lanes run it: they are taken
+        // from the first busy lane and added by all, so lane 0, which reports them, holds every
+        // trip's.  Added inside the branch, lane 0 only held the trips it was busy in: about half,
+        // which is what earlier rounds' splits left outside the event, the scan and the step.)
+        const unsigned long long pf_busy_m = __ballot(stage == RS_SCAN || stage == RS_STEP);
+        unsigned long long pf_dscan = 0, pf_dstep = 0;
+#endif
         if (stage == RS_SCAN || stage == RS_STEP) {
 #if HVP_REFILL_UNI_LDS && HVP_REFILL_UNI_TRIP
             const hvp::Consts& Ct = uni_view(U.C);
@@ -3336,11 +3388,18 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
             const hvp::Consts& Ct = C_arg;
 #endif
 #ifdef HVP_REFILL_PROF
-            gi_trip<N>(q, g, Ct, stage, fail, &pf_scan, &pf_step);
+            gi_trip<N>(q, g, Ct, stage, fail, &pf_dscan, &pf_dstep);
 #else
             gi_trip<N>(q, g, Ct, stage, fail);
 #endif
         }
+#ifdef HVP_REFILL_PROF
+        if (pf_busy_m) {
+            const int src = __ffsll((long long)pf_busy_m) - 1;
+            pf_scan += __shfl(pf_dscan, src, 64);
+            pf_step += __shfl(pf_dstep, src, 64);
+        }
+#endif
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -4418,13 +4477,18 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
     h->last_bnb = true;
 #ifdef HVP_REFILL_PROF
     if constexpr (N <= HVP_MAX_N_ENUM) {
-        unsigned long long hist[128];
+        unsigned long long hist[kPfHist];
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipMemcpyFromSymbol(hist, HIP_SYMBOL(g_pf_hist), sizeof(hist)));
         std::fprintf(stderr, "[refill-hist] node trips:");
         for (int i = 0; i < 64; ++i) std::fprintf(stderr, " %llu", hist[i]);
         std::fprintf(stderr, "\n[refill-hist] generation trips:");
         for (int i = 64; i < 128; ++i) std::fprintf(stderr, " %llu", hist[i]);
+        // per row id (hvp_gi.h: 6j + r, then 6N + 4m + r): scans in which the wave selects at it
+        if (HVP_REFILL_PROF_ROWS) {
+            std::fprintf(stderr, "\n[refill-hist] scans %llu, with a violating lane per row:", hist[128 + kPfRows]);
+            for (int i = 0; i < hvp::GiConstraintSet<N>::NC; ++i) std::fprintf(stderr, " %llu", hist[128 + i]);
+        }
         std::fprintf(stderr, "\n");
         std::memset(hist, 0, sizeof(hist));
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_pf_hist), hist, sizeof(hist)));
