@@ -47,6 +47,11 @@ Files (numpy .npz, no pickles):
                       the gear model (MpcGearCent)
   l1_long_*_N{9,10}.npz  min_1_norm at the MILP-vs-MIQP study's longer horizons (oracle branch
                       and bound, "method" = 1, "quadratic" = 0): t = 0 states, Q_du, a rollout
+  l1_long_n4_N{11,12,13,16}.npz  the seed-0 platoon's four local MILPs at the horizons where the
+                      templated device code changes path (l1_horizons; tests/test_horizons.py)
+  admm_horizon_N{8,9,12,13,16}.npz, admm_l1_horizon_N{9,12}.npz  naive ADMM around the node-record
+                      edge: the first-iteration local problems of the seed-0 platoon, at N = 12 also of
+                      five platoons whose leader ends in the top regions (admm_horizons)
   admm_l1_*.npz       naive ADMM with min_1_norm (LocalMpcADMM(quadratic_cost=False)): local problems
                       (incl. ConstantTime spacing), 3 closed-loop steps at n = 4, N = 5, and configs[2]'s
                       size (n = 10, N = 10, 20 iterations, 2 steps; "admm_l1 n10")
@@ -56,7 +61,8 @@ Files (numpy .npz, no pickles):
   l1batch_n10_N10.npz the benchmark's n = 10, N = 10 min_1_norm platoons (seeds 0..255), one vehicle
                       (seed % 10) each: oracle status, cost and sequence only (no params)
 Run:  python tests/golden/make_golden.py [sweep | gear | admm | admm_l1 [n10] | admm_gear | gadmm | cent [n10 | l1] | configs admm|gadmm
-                                          | l1 | l1_rollout | l1_long | l1stall | l1batch]
+                                          | l1 | l1_rollout | l1_long | l1stall | l1batch
+                                          | l1_horizons [N ...] | admm_horizons [N ...]]
 """
 
 from __future__ import annotations
@@ -73,7 +79,8 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import oracle as O  # noqa: E402
-from instances import decent_instances, leader_window, split_params  # noqa: E402
+from instances import (decent_instances, fast_leader_platoons, fast_leader_window, leader_window,  # noqa: E402
+                       split_params)
 
 
 def stop_and_go(N: int, t: int, p=3000.0, vh=20.0, vl=10.0, vf=30.0, c0=30, c1=50, L=200):
@@ -185,6 +192,27 @@ def l1_long():
         save("l1_long_rollout_n4_N10.npz", 10, [800.0], O.Cfg(), params, roles, si, exp, method=1, quadratic=0)
     finally:
         O.set_method(O.METHOD_ENUMERATE)
+
+
+L1_HORIZONS = (11, 12, 13, 16)
+
+
+def l1_horizons(only=()):
+    """min_1_norm at the horizons where the templated code changes path (tests/test_horizons.py):
+    N = 11, 12 (naive-ADMM node records, 48-bit codes), 13 (neither) and 16 (HVP_MAX_N, the code word
+    full).  The four local MILPs of the seed-0 platoon (n = 4) each, the oracle's branch and bound, one
+    process per instance.  Files l1_long_n4_N{11,12,13,16}.npz in the l1_long_* layout.
+    Generation (wall clock on 8 cores, the four instances in parallel): N = 11 11 s, N = 12 23 s,
+    N = 13 46 s, N = 16 868 s (all four instances: under the 20 minutes that would have cut it to two)."""
+    import time
+
+    for N in (only or L1_HORIZONS):
+        t0 = time.time()
+        p, r = decent_instances(O.env_initial_state(4, 0), N, leader_window(N))
+        exp = _l1_bnb_solve(N, p, r)
+        save(f"l1_long_n4_N{N}.npz", N, [800.0], O.Cfg(), p, r, np.zeros(len(r), np.int32), exp, method=1,
+             quadratic=0)
+        print(f"  N = {N}: {time.time() - t0:.0f} s", flush=True)
 
 
 def _l1_bnb_init():
@@ -480,6 +508,55 @@ def admm_l1_fixtures(big: bool = False):
         print("admm_l1_steps_n4_N5.npz written")
 
 
+ADMM_HORIZONS = (8, 9, 12, 13, 16)
+ADMM_L1_HORIZONS = (9, 12)
+
+
+def _admm_case(job):
+    N, role, p, quadratic = job
+    return O.solve_admm_miqp(O.gear_pwa_system(800.0), O.Cfg(), N, role, 0.5, p, 200, quadratic)
+
+
+def admm_horizons(only=()):
+    """Naive ADMM at the horizons around the node-record edge (tests/test_horizons.py): the local
+    problems of the FIRST ADMM iteration of a time step (y = z = 0, fleet_naive_admm.py:379-419) of
+    the seed-0 platoon (n = 4), in the admm_local_* layout.  admm_horizon_N{8,9,12,13,16}.npz
+    (quadratic; N = 12 also holds the five fast_leader_platoons, "n_seed" = 4 marks where they start)
+    and admm_l1_horizon_N{9,12}.npz (min_1_norm).  Generation (wall clock, 4 processes): quadratic
+    under 1 / 1 / 7 / 3 / 5 s; min_1_norm 14 s and 32 s."""
+    import time
+    from multiprocessing import Pool
+
+    with Pool(min(4, os.cpu_count() or 1)) as pool:
+        for quadratic, horizons in ((True, ADMM_HORIZONS), (False, ADMM_L1_HORIZONS)):
+            for N in horizons:
+                if only and N not in only:
+                    continue
+                t0 = time.time()
+                zero = np.zeros((2, N + 1))
+                platoons = [(O.env_initial_state(4, 0).astype(float), leader_window(N))]
+                if quadratic and N == 12:
+                    platoons += [(st, fast_leader_window(N, st[0])) for st in fast_leader_platoons()]
+                P, R = [], []
+                for st, lead in platoons:
+                    for i in range(4):
+                        P.append(O.admm_params(st[2 * i:2 * i + 2], zero, zero, zero, zero, lead if i == 0 else zero))
+                        R.append(O.role_bits(i, 4))
+                res = pool.map(_admm_case, [(N, r, p, quadratic) for r, p in zip(R, P)], chunksize=1)
+                name = f"admm_horizon_N{N}.npz" if quadratic else f"admm_l1_horizon_N{N}.npz"
+                np.savez_compressed(os.path.join(HERE, name), N=N, rho=0.5, quadratic=int(quadratic), n_seed=4,
+                                    cfg=O.Cfg().vector(), params=np.array(P), roles=np.array(R, np.int32),
+                                    exp_x=np.array([r.x for r in res]), exp_u=np.array([r.u for r in res]),
+                                    exp_xf=np.array([r.x_front for r in res]),
+                                    exp_xb=np.array([r.x_back for r in res]),
+                                    exp_cost=np.array([r.cost for r in res]),
+                                    exp_status=np.array([r.status for r in res], np.int32),
+                                    exp_cert=np.array([r.certified for r in res]),
+                                    exp_region=np.array([r.sigma for r in res], np.int32))
+                print(f"{name}: {len(R)} instances, optimal {sum(r.status == 0 for r in res)}, "
+                      f"{time.time() - t0:.0f} s", flush=True)
+
+
 def admm_gear_fixtures():
     """Naive ADMM with LocalMpcGear (fleet_naive_admm.py:261-288, selected for pwa_friction at
     :632-633): the local problem's modes are (gear, friction region) pairs (oracle
@@ -747,6 +824,12 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "l1_long":
         l1_long()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "admm_horizons":
+        admm_horizons([int(a) for a in sys.argv[2:]])
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "l1_horizons":
+        l1_horizons([int(a) for a in sys.argv[2:]])
         return
     if len(sys.argv) > 1 and sys.argv[1] == "l1stall":
         l1_stall()

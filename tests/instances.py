@@ -30,6 +30,24 @@ def decent_instances(state: np.ndarray, N: int, lead: np.ndarray, leader_index: 
     return np.array(P), np.array(R, dtype=np.int32)
 
 
+def fast_leader_platoons() -> list[np.ndarray]:
+    """Five 4-vehicle platoon states at 18..21 m/s whose leader's reference runs 400 m ahead at 40 m/s
+    (fast_leader_window): the leading vehicle accelerates through the velocity bands over the horizon,
+    so its optimal sequence starts in region 3 and ends in region 5 (N = 12) or 6 (N = 16) -- the top
+    nibble of the 48- and 64-bit region codes (tests/test_horizons.py, the admm_horizon_N12 fixture)."""
+    out = []
+    for j, (v, gap) in enumerate((((18, 19, 20, 21), 70), ((21, 20, 19, 18), 60), ((19.5, 18.5, 20.5, 19), 90),
+                                  ((20, 21, 18, 19), 80), ((18.5, 20.5, 19.5, 21), 65))):
+        p = 3000.0 - gap * np.arange(4) - 10.0 * j
+        out.append(np.stack([p, np.array(v, float)], 1).reshape(-1))
+    return out
+
+
+def fast_leader_window(N: int, p0: float) -> np.ndarray:
+    """A leader reference 400 m ahead of p0 at 40 m/s, window [0, N]."""
+    return np.stack([p0 + 400.0 + 40.0 * np.arange(N + 1), np.full(N + 1, 40.0)])
+
+
 def split_params(p: np.ndarray, N: int):
     K = 2 * (N + 1)
     return p[:2], p[2:2 + K].reshape(2, N + 1), p[2 + K:2 + 2 * K].reshape(2, N + 1), p[2 + 2 * K:].reshape(2, N + 1)
