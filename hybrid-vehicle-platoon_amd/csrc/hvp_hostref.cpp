@@ -302,6 +302,15 @@ int admm_warm_solve(hvp::LaneQp<N>& q, const hvp_system& S, const hvp::Consts& C
     return hvp::GI_FAIL_ITER;
 }
 
+// What hvp_hostref_bnb_leaves reports of one search: the greedy dive's sequence where its leaf QP
+// converged, and the sequences of level N's list.
+struct BnbTrace {
+    int dive_ok = 0;
+    uint64_t dive_code = 0;
+    std::vector<uint64_t> leaves;
+};
+thread_local BnbTrace* t_bnb_trace = nullptr;
+
 // Branch and bound (hvp_bnb.h) with the same level-synchronous order as the gfx950 kernels:
 // root bound + greedy dive, then per depth the children of the unpruned nodes, then the argmin
 // and tie rule over the leaves.
@@ -454,7 +463,10 @@ void solve_one_bnb(const hvp_system& S, const hvp::Consts& C, int role, const do
             uint64_t code;
             double c1;
             uint64_t dhs = root.hs;
-            if (hvp::bnb_dive<N>(S, C, v0, root.y, &code) && qp(code, N, 0.0, -1.0, c1, nullptr, &dhs)) inc = c1;
+            if (hvp::bnb_dive<N>(S, C, v0, root.y, &code) && qp(code, N, 0.0, -1.0, c1, nullptr, &dhs)) {
+                inc = c1;
+                if (t_bnb_trace) t_bnb_trace->dive_ok = 1, t_bnb_trace->dive_code = code;
+            }
             if (C.l1 && g_l1_solver == 1 && N <= HVP_MAX_N_ENUM) {
                 // the simplex's root optimum is a vertex (an extreme point where the LP optimum is a
                 // face): a second dive towards the constant-velocity trajectory (k_lp_root)
@@ -492,6 +504,8 @@ void solve_one_bnb(const hvp_system& S, const hvp::Consts& C, int role, const do
             }
         }
         if (k == N) nleaves += (int)nxt.size();
+        if (k == N && t_bnb_trace)
+            for (const Node& c : nxt) t_bnb_trace->leaves.push_back(c.code);
         root_phase = false;
         if (!claim.empty())
             for (const Node& c : nxt) {
@@ -849,6 +863,33 @@ int hvp_hostref_candidates(const hvp_problem* P, const hvp_system* S, int role, 
 #undef HVP_CASE
         default: return HVP_E_UNSUPPORTED;
     }
+    return n;
+}
+
+// The branch and bound of one instance, for its greedy dive and level N's list (test use only):
+// *dive_ok = 1 and *dive_code = the dive's sequence (4 bits per step) where the dive reached a leaf
+// whose QP converged; leaf_code[0 .. min(n, cap)) = the sequences of level N's nodes in list order.
+// Returns n, the length of that list.
+int hvp_hostref_bnb_leaves(const hvp_problem* P, const hvp_system* S, int role, const double* prm, int32_t* dive_ok,
+                           uint64_t* dive_code, uint64_t* leaf_code, int cap) {
+    const hvp::Consts C = make_consts(*P);
+    double u[HVP_MAX_N], x[2 * (HVP_MAX_N + 1)], cost;
+    int8_t reg[HVP_MAX_N];
+    int32_t st, nodes, it;
+    BnbTrace tr;
+    t_bnb_trace = &tr;
+    switch (P->N) {
+#define HVP_CASE(k) \
+    case k: solve_one_bnb<k>(*S, C, role, prm, u, x, reg, &cost, &st, &nodes, &it); break;
+        HVP_CASE(2) HVP_CASE(3) HVP_CASE(4) HVP_CASE(5) HVP_CASE(6) HVP_CASE(7) HVP_CASE(8)
+#undef HVP_CASE
+        default: t_bnb_trace = nullptr; return HVP_E_UNSUPPORTED;
+    }
+    t_bnb_trace = nullptr;
+    *dive_ok = tr.dive_ok;
+    *dive_code = tr.dive_code;
+    const int n = (int)tr.leaves.size();
+    for (int i = 0; i < n && i < cap; ++i) leaf_code[i] = tr.leaves[i];
     return n;
 }
 }

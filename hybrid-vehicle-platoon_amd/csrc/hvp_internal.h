@@ -32,8 +32,12 @@ struct Workspace {
     int64_t cap = 0;
     int32_t* inst_off = nullptr;   // [max_batch] first candidate slot (-1: overflow)
     int32_t* inst_cnt = nullptr;   // [max_batch] candidates of the instance
-    int32_t* inst_flag = nullptr;  // [max_batch] 0 ok, 1 infeasible constant rows
-    unsigned long long* counter = nullptr;  // [8] reserved slots, qp iterations, fallback count, root QPs, failed bounds
+    int32_t* inst_flag = nullptr;  // [max_batch] 0 ok, 1 infeasible constant rows (2 overflow, 4 / 8 unresolved
+                                   // leaves, 16 the dive's leaf stands for its level-N copy: hvp_lane.h)
+    unsigned long long* counter = nullptr;  // [8] reserved slots (branch and bound: dead slots of the level
+                                            // lists), qp iterations, fallback count, root QPs, failed bounds,
+                                            // spills, pass-through nodes, [7] reused dive leaves (Workspace::reuse;
+                                            // the 16-lane path's leaf-list length)
     int32_t* redo = nullptr;       // [cap] candidates the active-set method hands to the IPM
     int32_t* task_inst = nullptr;  // [cap]
     uint32_t* task_code = nullptr; // [cap]
@@ -74,7 +78,8 @@ struct Workspace {
     double* dv_lb = nullptr;                     // [max_batch] leaf cost
     int32_t* dv_stat = nullptr;                  // [max_batch]
     double* dv_y = nullptr;                      // [max_batch * N]
-    int32_t* dv_redo = nullptr;                  // [max_batch] (failed dives are not re-solved)
+    int32_t* dv_redo = nullptr;                  // [max_batch] the leaf QP's active-set steps (failed dives
+                                                 // are not re-solved: no redo list)
     unsigned long long* dv_lvl = nullptr;        // [(2 + 4)(HVP_MAX_N + 1)] counts / claims of the dive list
     unsigned long long* dv_counter = nullptr;    // [8]
     char* dv_mem = nullptr;                      // the allocation the dv_* arrays live in
@@ -83,6 +88,10 @@ struct Workspace {
     int split_shift = 0;                         // log2(split): a bucket's segment is cap >> split_shift
     int pass = 0;                                // pass-through nodes (hvp_lane.h bnb_put_children;
                                                  // HVP_PASS_THROUGH=1 turns them on, launch_bnb)
+    int reuse = 0;                               // the greedy dive's leaf stands for its level-N copy
+                                                 // (decentralised lane path with the dive list; the
+                                                 // refill event at level N - 1, k_bnb_key / _write /
+                                                 // _finish; HVP_DIVE_REUSE=0 turns it off, launch_bnb)
     // naive-ADMM node records (16-lane path, 8 < N <= 12; hvp_lane.h node_index): the final hinge
     // states, active set and factors of every tree node's QP, for the same node in the next solve
     void* nrec = nullptr;                        // [max_batch][N + 1][nslots] hvp::coop::WarmRec<N>
@@ -93,7 +102,8 @@ struct Workspace {
     int norder = 0;                              // k_bnb_bound_coop takes the level in k_node_order's order
     int32_t* win = nullptr;                      // [max_batch] the winning leaf's slot in level N's list
                                                  // (k_bnb_write), read by k_bnb_finish, which writes
-                                                 // every per-instance output in instance order
+                                                 // every per-instance output in instance order; ~i:
+                                                 // instance i's dive entry won (Workspace::reuse)
 };
 
 
@@ -114,6 +124,7 @@ struct hvp_handle {
     bool bnb = false;       // search method resolved at hvp_create (HVP_METHOD_*)
     bool last_bnb = false;
     int last_split = 1;  // buckets of the last B&B solve's level lists (Workspace::split)
+    bool last_reuse = false;  // the last B&B solve ran with Workspace::reuse (counter[7]: reused leaves)
     int n_cu = 256;
     // host-pointer entry point staging (grown on demand)
     size_t stage_bytes = 0;

@@ -644,7 +644,11 @@ int hvp_get_stats(hvp_handle* h, hvp_stats* out) {
                 n += (int64_t)std::min(b == 0 ? lv[k] : lv[(1 + b) * M + k], b + 1 < nb ? seg : cap - (nb - 1) * seg);
         // less the pass-through nodes (counter[6]): listed, but their parent's QP is theirs
         // (hvp_lane.h bnb_put_children kPassFlag)
-        out->n_candidates = n - (int64_t)c[6];
+        // and the dead slots of reservations that ran past a segment's end (counter[0] here)
+        out->n_candidates = n - (int64_t)c[6] - (int64_t)c[0];
+        // plus the dive leaves that stand for their level-N nodes (counter[7], Workspace::reuse):
+        // nodes of the tree that are not listed
+        if (h->last_reuse) out->n_candidates += (int64_t)c[7];
         // QP time = K_bnb_root + every K_bnb_bound launch (the expand / select kernels excluded)
         float sum = 0.f;
         for (int k = 0; k <= h->prob.N; ++k) {

@@ -1477,6 +1477,9 @@ __device__ inline int bnb_put_children(const Workspace& ws, int lv, unsigned lon
     const int nc = __popc(mask), d = lv & 1;
     if (off + nc > limit) {
         for (unsigned long long t = off; t < limit && t < off + nc; ++t) ws.nd_inst[d][t] = -1;
+        // (dead slots are listed and are no nodes: counter[0], free in the branch and bound, takes
+        // them out of hvp_stats.n_candidates)
+        if (off < limit) atomicAdd(&ws.counter[0], limit - off);
         bool placed = false;
 #ifndef HVP_SPILL
 #define HVP_SPILL 1
@@ -1494,6 +1497,7 @@ __device__ inline int bnb_put_children(const Workspace& ws, int lv, unsigned lon
                     atomicAdd(&ws.counter[5], 1ull);  // hvp_stats.n_spilled
                 } else {
                     for (unsigned long long t = o; t < end; ++t) ws.nd_inst[d][t] = -1;
+                    if (o < end) atomicAdd(&ws.counter[0], end - o);
                 }
             }
         }
@@ -1589,8 +1593,9 @@ struct LevelList {
 };
 __device__ inline LevelList level_list(const Workspace& ws, int k) {
     LevelList L;
-    L.nb = ws.split > 1 ? ws.split : 1;
-    L.seg = (unsigned long long)ws.cap >> ws.split_shift;
+    // (level 0, the roots, is one list whatever the split: k_inst_prep writes it in instance order)
+    L.nb = ws.split > 1 && k > 0 ? ws.split : 1;
+    L.seg = k > 0 ? (unsigned long long)ws.cap >> ws.split_shift : (unsigned long long)ws.cap;
 #pragma unroll
     for (int b = 0; b < kMaxBuckets; ++b) {
         const unsigned long long v = b < L.nb ? *bucket_count(ws, b, k) : 0ull;
@@ -2692,6 +2697,9 @@ __device__ inline void bnb_node_done(int k, long long t, int inst, bool ok, int 
         ws.leaf_stat[t] = ok ? 0 : HVP_MAXITER;
 #pragma unroll
         for (int j = 0; j < N; ++j) ws.task_y[t * N + j] = y[j];
+        // the dive list's leaf (entry t = inst): its steps, for the level-N copy it may stand for
+        // (Workspace::reuse)
+        if (ws.lvl == ws.dv_lvl) ws.dv_redo[t] = its;
         if (ok) {
             atomicMin(&ws.inc[inst], cost_key(c));
         } else if (ws.lvl != ws.dv_lvl) {
@@ -3201,7 +3209,7 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
     uint64_t code = 0;
     unsigned nmask = 0;  // regions the lane's node can take at step k (its set-up's relax_step)
     bool exhausted = false;
-    unsigned long long iter_sum = 0, pass_n = 0;
+    unsigned long long iter_sum = 0, pass_n = 0;  // (pass_n: pass-through nodes | reused dive leaves << 32)
 #ifdef HVP_REFILL_PROF  // diagnostics build: event / trip cycles and busy lane-trips per wave
     unsigned long long pf_ev = 0, pf_all = 0, pf_busy = 0, pf_trips = 0, pf_wb = 0, pf_cl = 0, pf_dc = 0, pf_rs = 0;
     unsigned long long pf_scan = 0, pf_step = 0;
@@ -3288,6 +3296,26 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
 #else
                     cmask = bnb_children(tab[sys[inst]], C, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
 #endif
+                }
+            }
+            if (k + 1 == N && ws.reuse && cmask) {
+                // The child that is the greedy dive's sequence is the dive list's leaf over again (the
+                // same code, K = N: the same QP, steps and bits), and its parent is never pruned
+                // before level N: every ancestor's bound is a relaxation of that leaf's QP, whose cost
+                // is the incumbent until the first level-N leaf.  Where that leaf's QP succeeded the
+                // child is not written: the dive entry stands for it in the tie rule (flag 16:
+                // k_bnb_key, k_bnb_write, k_bnb_finish) and in the tree's counts.  A failed dive leaf
+                // is written as before: its level-N copy raises flag 8 and goes to k_bnb_ipm.
+                const uint64_t dcode = ws.dv_code[inst];
+                const int dstat = ws.dv_stat[inst];  // (nonzero too where the instance did not dive)
+                constexpr uint64_t kPrefix = (1ull << (hvp::kCodeBits * (N - 1))) - 1;
+                const unsigned bit = 1u << hvp::code_region(dcode, N - 1);
+                if (dstat == 0 && ((dcode ^ code) & kPrefix) == 0 && (cmask & bit)) {
+                    cmask &= ~bit;
+                    atomicOr(&ws.inst_flag[inst], 16);
+                    atomicAdd(&ws.nodes[inst], 1);
+                    atomicAdd(&ws.iters[inst], ws.dv_redo[inst]);
+                    pass_n += 1ull << 32;  // (the high half: reused leaves)
                 }
             }
             if (k < N) {
@@ -3407,7 +3435,10 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
         pass_n += __shfl_down(pass_n, off, 64);
     }
     if (lane == 0 && iter_sum) atomicAdd(&ws.counter[1], iter_sum);
-    if (lane == 0 && pass_n) atomicAdd(&ws.counter[6], pass_n);  // pass-through nodes (no QP; hvp_get_stats)
+    // pass-through nodes (no QP; hvp_get_stats) and, in the high half, the dive leaves that stand
+    // for their level-N copies (QPs of the tree that ran once)
+    if (lane == 0 && (pass_n & 0xffffffffull)) atomicAdd(&ws.counter[6], pass_n & 0xffffffffull);
+    if (lane == 0 && (pass_n >> 32)) atomicAdd(&ws.counter[7], pass_n >> 32);
 #ifdef HVP_REFILL_PROF
     pf_all = __builtin_amdgcn_s_memtime() - pf_t0;
     if (lane == 0) {  // the claim slots of levels > N are free (prof builds need N <= 6)
@@ -3634,10 +3665,19 @@ __global__ __launch_bounds__(kBnbBlock<N>) void k_bnb_ipm(const hvp_system* __re
 }
 
 // tie rule: the lexicographically first leaf within 1e-9 relative of the minimum
+// n_dive: entries of the dive list (one per instance) to scan as well, 0 without Workspace::reuse.
+// The entry of an instance with flag 16 is the level-N leaf that the refill event did not write
+// (its QP succeeded), under the same rule.
 template <int N>
-__global__ __launch_bounds__(kBlock) void k_bnb_key(Workspace ws, int form, int l1) {
+__global__ __launch_bounds__(kBlock) void k_bnb_key(Workspace ws, int form, int l1, int n_dive) {
     const int src = N & 1;
     const LevelList lvl = level_list(ws, N);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_dive; i += gridDim.x * blockDim.x) {
+        if (!(ws.inst_flag[i] & 16)) continue;
+        const double best = inc_of(ws, i);
+        if (ws.dv_lb[i] <= best + 1e-9 * fmax(1.0, fabs(best)))
+            atomicMin(&ws.key[i], (unsigned long long)hvp::bnb_lexkey(ws.dv_code[i], N));
+    }
 #pragma unroll
     for (int b = 0; b < kMaxBuckets; ++b)
     for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < (long long)lvl.n[b];
@@ -3726,9 +3766,15 @@ __device__ inline void write_copies(int i, const hvp_system& S, const hvp::Const
 // waves -- on other XCDs -- complete: 116 MB of HBM writes per C2 solve for ~25 MB of outputs,
 // profiles/r05zc.)
 template <int N>
-__global__ __launch_bounds__(kBlock) void k_bnb_write(Workspace ws) {
+__global__ __launch_bounds__(kBlock) void k_bnb_write(Workspace ws, int n_dive) {
     const int src = N & 1;
     const LevelList lvl = level_list(ws, N);
+    // a winning dive entry (k_bnb_key's n_dive): ~i, which no slot of the list is.  The instance's
+    // level-N leaves all have other sequences, so one writer per instance remains.
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_dive; i += gridDim.x * blockDim.x) {
+        if (!(ws.inst_flag[i] & 16)) continue;
+        if (hvp::bnb_lexkey(ws.dv_code[i], N) == ws.key[i]) ws.win[i] = ~i;
+    }
 #pragma unroll
     for (int b = 0; b < kMaxBuckets; ++b)
     for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < (long long)lvl.n[b];
@@ -3782,17 +3828,21 @@ __global__ __launch_bounds__(kBlock) void k_bnb_finish(int B, const hvp_system* 
         if (C.form == HVP_FORM_ADMM) write_copies<N>(i, S, C, role[i], prm, false, nullptr, xf_out, xb_out);
         return;
     }
-    // the winner recorded by k_bnb_write
+    // the winner recorded by k_bnb_write: a slot of level N's list, or the instance's dive entry
+    // (~i, only with Workspace::reuse)
     const int src = N & 1;
-    const long long t = ws.win[i];
-    const uint64_t code = ws.nd_code[src][t];
+    const int w = ws.win[i];
+    const bool dive = ws.reuse && w < 0;
+    const long long t = dive ? (long long)i : (long long)w;
+    const uint64_t code = dive ? ws.dv_code[t] : ws.nd_code[src][t];
+    const double* ty = dive ? ws.dv_y : ws.task_y;
     double y[N];
 #pragma unroll
-    for (int j = 0; j < N; ++j) y[j] = ws.task_y[t * N + j];
+    for (int j = 0; j < N; ++j) y[j] = ty[t * N + j];
     write_solution<N>(i, S, prm, true, code, y, u_out, x_out, region_out, gear_out);
     // (the min_1_norm copies come from the winner's LP: k_l1_admm_write)
     if (C.form == HVP_FORM_ADMM && !C.l1) write_copies<N>(i, S, C, role[i], prm, true, y, xf_out, xb_out);
-    if (cost_out) cost_out[i] = ws.nd_lb[src][t];
+    if (cost_out) cost_out[i] = dive ? ws.dv_lb[t] : ws.nd_lb[src][t];
 }
 
 // ================================================================== fixed-control evaluation
@@ -4250,6 +4300,21 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
     // HVP_PASS_THROUGH=1 turns them on
     const char* pt = std::getenv("HVP_PASS_THROUGH");
     ws.pass = pt && pt[0] == '1';
+    // the root level and the dives' leaves through the refill kernel (below); HVP_ROOT_REFILL=0
+    // selects k_bnb_root (A/B), and so does a workspace that cannot hold the root level (one list
+    // whatever the split, level_list: a capacity that fits the tree with one list per level fits it
+    // with buckets too, which k_bnb_root's tree, with the dive's leaf listed again, need not)
+    const char* rr = std::getenv("HVP_ROOT_REFILL");
+    const bool root_refill = fused && !(rr && rr[0] == '0') && ws.dv_mem &&
+                             (unsigned long long)ws.cap >= (unsigned long long)B;
+    // The dive's leaf is a level-N node of the tree (its ancestors are never pruned), and level N
+    // solved it a second time: 163,840 of 2,069,224 QPs per flagship step, all in the longest
+    // launch.  With the dive list present the refill event at level N - 1 leaves that child out
+    // and the dive entry takes its place in the tie rule and the counts (k_bnb_bound_refill,
+    // k_bnb_key).  HVP_DIVE_REUSE=0: every leaf of level N is solved there (A/B)
+    const char* dr = std::getenv("HVP_DIVE_REUSE");
+    ws.reuse = root_refill && !(dr && dr[0] == '0');
+    h->last_reuse = ws.reuse != 0;
     if (fused) {
         // the refill kernel's workspace descriptors ([0] the level lists, [1] the dive list in
         // place of level N's), uploaded when they change
@@ -4369,11 +4434,7 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
             // The tree is k_bnb_root's: the root's children are never pruned (the root bound is <=
             // every leaf), and the dives' incumbents are in place before level 1.  The refill kernel
             // keeps every lane busy where k_bnb_root (one lane per instance, 1 wave per SIMD) waits
-            // for each wave's slowest root + dive.  HVP_ROOT_REFILL=0 selects k_bnb_root (A/B);
-            // so does a workspace whose bucket segment cannot hold the root level.
-            const char* rr = std::getenv("HVP_ROOT_REFILL");
-            const bool root_refill = !(rr && rr[0] == '0') && ws.dv_mem &&
-                                     ((unsigned long long)ws.cap >> ws.split_shift) >= (unsigned long long)B;
+            // for each wave's slowest root + dive.  (root_refill: above.)
             if (root_refill) {
                 const int g_root = (int)std::min<long long>((B + BS - 1) / BS, (long long)h->n_cu * kRefillBlocksPerCu);
                 launch_refill<N>(h, g_root, lds, st, 0, sys, role, params, 0);
@@ -4457,9 +4518,10 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
                                h->d_sys, sys, role, params, h->C, ws);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_bnb_key<N>, dim3(g_small), dim3(kBlock), 0, st, ws, h->C.form, h->C.l1);
+    const int n_dive = ws.reuse ? B : 0;  // the dive entries in the tie rule (every other form: none)
+    hipLaunchKernelGGL(k_bnb_key<N>, dim3(g_small), dim3(kBlock), 0, st, ws, h->C.form, h->C.l1, n_dive);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bnb_write<N>, dim3(g_small), dim3(kBlock), 0, st, ws);
+    hipLaunchKernelGGL(k_bnb_write<N>, dim3(g_small), dim3(kBlock), 0, st, ws, n_dive);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_bnb_finish<N>, dim3(grid_for(B)), dim3(kBlock), 0, st, B, h->d_sys, sys, role, params, h->C,
                        ws, u_out, x_out, region_out, gear_out, cost_out, status_out, nodes_out, iters_out, xf_out,

@@ -175,7 +175,13 @@ typedef struct hvp_handle hvp_handle;
 typedef struct hvp_stats {
     int64_t n_instances;    /* instances in the last solve                            */
     int64_t n_candidates;   /* region sequences (QPs) solved in the last solve         */
-    int64_t qp_iterations;  /* sum of QP iterations (active-set + fallback IPM)      */
+                            /* (branch and bound: the tree's nodes -- a greedy-dive    */
+                            /* leaf that also stands for its level-N node counts as    */
+                            /* both, as when that node was solved again)               */
+    int64_t qp_iterations;  /* sum of QP iterations (active-set + fallback IPM) that   */
+                            /* ran: a dive leaf reused for its level-N node adds its   */
+                            /* steps once (the per-instance iters output adds them per */
+                            /* tree node, so the outputs' sum can exceed this figure)  */
     int64_t capacity;       /* candidate workspace                                     */
     double last_ms;         /* device time of the last solve (event-timed), ms         */
     double qp_ms;           /* device time of its QP kernel (K_qp), ms                 */
