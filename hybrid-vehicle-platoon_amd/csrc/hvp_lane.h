@@ -2679,13 +2679,16 @@ __device__ inline bool setup_node_batch(Q& q, const hvp_system* tab, const int32
     return ok;
 }
 
-template <int N>
+// LEAF / UPPER: the caller's level is known to be N / below N (k_bnb_bound_refill's phases), and
+// only that side of the write-back is instantiated
+template <int N, bool LEAF = false, bool UPPER = false>
 __device__ inline void bnb_node_done(int k, long long t, int inst, bool ok, int its, double c, const double* y,
                                      const hvp::Consts& C, const Workspace& ws) {
+    static_assert(!(LEAF && UPPER), "one phase");
     const int dst = k & 1;
     atomicAdd(&ws.nodes[inst], 1);
     atomicAdd(&ws.iters[inst], its);
-    if (k < N) {
+    if (UPPER || (!LEAF && k < N)) {
         ws.nd_lb[dst][t] = ok ? c : -1e300;  // a failed bound QP prunes nothing
         if (!ok) atomicAdd(&ws.counter[4], 1ull);
         if (k == 0 && ok) {  // the root's optimum: the greedy dive's target (k_bnb_dive_prep)
@@ -3163,16 +3166,57 @@ __device__ inline const T& uni_view(const T& obj) {
     asm volatile("" : "+s"(off));
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(&obj) + off);
 }
+// Phases.  The level k is a run-time argument, and a launch of one level carried the code and the
+// registers of every kind of level.  PH says which levels an instantiation serves, and the event
+// leaves out of its source path what those cannot reach (launch_refill picks it from k):
+//   RP_ANY    every level: the kernel before, line for line.
+//   RP_LEAF   k == N, a constant (level N and the dive list).  A leaf has no children: no child
+//             mask (nmask, cmask, clb), no pruning test, no split_reserve / bnb_put_children, no
+//             reuse block, no relaxed step in its set-up.  No RS_PASS either: a level-N slot never
+//             carries kPassFlag (bnb_put_children is called with pass = -1 at k + 1 == N, and
+//             k_bnb_dive_prep's codes are bnb_dive's, plain region digits).
+//   RP_UPPER  k + 1 < N, k at run time (levels 0..N-2): no leaf write-back (leaf_stat, task_y of a
+//             leaf, the incumbent's atomicMin, the redo list), no reuse block.
+// Level N - 1, the only one that enters the reuse block, runs RP_ANY.
+// The statements that remain are the same, in the same order: results are bit-equal.
+// HVP_REFILL_PH_LEAF / _UPPER: 0 sends that phase's launches through RP_ANY (the code before);
+// at run time HVP_REFILL_PHASES=0 does so for both (launch_bnb; tests, A/B).
+#ifndef HVP_REFILL_PH_LEAF
+#define HVP_REFILL_PH_LEAF 1
+#endif
+#ifndef HVP_REFILL_PH_UPPER
+#define HVP_REFILL_PH_UPPER 1
+#endif
+#ifndef HVP_REFILL_PH_PRELEAF
+#define HVP_REFILL_PH_PRELEAF 0  // (no instantiation of its own: level N - 1 keeps RP_ANY)
+#endif
+enum { RP_ANY = 0, RP_LEAF = 1, RP_UPPER = 2 };
+// Which instantiations ship: those whose trip section (the stretch without a global access) has no
+// more instructions, scratch instructions or v_readlanes than RP_ANY's in the same build, at the
+// same waves per SIMD and LDS (profiles/r11a_refill_phase_static.txt, profiles/refill_static.py).
+// The register allocation of the trip moves with every edit of the event, although the trip's
+// source is the same in all three: a pair that misses keeps RP_ANY.  Bit N of [STAGE].
+constexpr int kRefillPhaseMaxN = HVP_MAX_N_ENUM;  // (the refill path's horizons)
+constexpr unsigned kRefillLeafOk[2] = {1u << 2 | 1u << 3 | 1u << 5 | 1u << 6 | 1u << 7 | 1u << 8,
+                                       1u << 2 | 1u << 3 | 1u << 5 | 1u << 6 | 1u << 8};
+constexpr unsigned kRefillUpperOk[2] = {1u << 3 | 1u << 4, 1u << 3 | 1u << 4 | 1u << 5 | 1u << 8};
+template <int N, bool STAGE>
+constexpr bool kRefillPhLeaf = HVP_REFILL_PH_LEAF && N <= kRefillPhaseMaxN && ((kRefillLeafOk[STAGE] >> N) & 1u);
+template <int N, bool STAGE>
+constexpr bool kRefillPhUpper = HVP_REFILL_PH_UPPER && N <= kRefillPhaseMaxN && ((kRefillUpperOk[STAGE] >> N) & 1u);
 #if HVP_REFILL_BYVAL
 // (round 3's kernel body: the descriptor and the constants as by-value kernel arguments, the
 // level list hoisted)
-template <int N, bool STAGE>
+template <int N, bool STAGE, int PH = RP_ANY>
 __global__ __launch_bounds__(kBnbBlock<N>) __attribute__((amdgpu_waves_per_eu(HVP_REFILL_WAVES)))
-void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys, const int32_t* __restrict__ sys,
+void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n_sys, const int32_t* __restrict__ sys,
                         const int32_t* __restrict__ role, const double* __restrict__ params, hvp::Consts C_arg,
                         Workspace ws_arg) {
     constexpr int BS = kBnbBlock<N>;
     static_assert(N <= HVP_MAX_N_ENUM, "lane refill is the N <= 8 path");
+    constexpr bool kLeaf = PH == RP_LEAF, kUpper = PH == RP_UPPER;
+    const int k = kLeaf ? N : k_arg;
+    if constexpr (kUpper) __builtin_assume(k + 1 < N);
     constexpr bool kUniEvent = kRefillUniEvent<N>;
     __shared__ RefillUni s_uni;  // (takes no LDS where nothing below uses it)
     const RefillUni& U = s_uni;
@@ -3253,7 +3297,7 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
             unsigned cmask = 0;  // children of a finished bound node (k_bnb_expand's work, fused)
             double clb = 0.0;
             int csteps = 0;      // the finished node's active-set steps (its children's bucket)
-            if (done && stage == RS_PASS) {
+            if (!kLeaf && done && stage == RS_PASS) {  // (no level-N slot is a pass-through node)
                 // a pass-through node: its QP is its parent's (bound inherited in nd_lb), so only its
                 // children are written.  A tree node all the same (nodes_out, the NodeCount
                 // analogue); hvp_stats.n_candidates counts QPs and leaves it out (counter[6])
@@ -3268,7 +3312,7 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
                 const bool ok = st == hvp::GI_OK;
                 // the incumbent's key, fetched with the cost's row (only leaves move it, and a launch
                 // of level k < N runs none; at k == N it is not read)
-                constexpr bool kInc = kRefillDcBatch<N> && HVP_REFILL_INC_BATCH;
+                constexpr bool kInc = kRefillDcBatch<N> && HVP_REFILL_INC_BATCH && !kLeaf;
                 unsigned long long inck = 0;
                 if (kInc && !ok) inck = ws.inc[inst];
                 const double c = ok ? hvp::direct_cost<N, kRefillDcBatch<N>>(
@@ -3284,8 +3328,9 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
                     pf_dc += __builtin_amdgcn_s_memtime() - pf_e0;
                 }
 #endif
-                bnb_node_done<N>(k, t, inst, ok, g.iter, c, q.y, C, ws);
+                bnb_node_done<N, kLeaf, kUpper>(k, t, inst, ok, g.iter, c, q.y, C, ws);
                 stage = RS_IDLE;
+                if constexpr (!kLeaf) {
                 // the incumbent only changes at the leaves (level N): below N this pruning test
                 // sees the value a separate expand kernel would
                 clb = ok ? c : -1e300;
@@ -3297,7 +3342,9 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
                     cmask = bnb_children(tab[sys[inst]], C, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
 #endif
                 }
+                }
             }
+            if constexpr (PH == RP_ANY)
             if (k + 1 == N && ws.reuse && cmask) {
                 // The child that is the greedy dive's sequence is the dive list's leaf over again (the
                 // same code, K = N: the same QP, steps and bits), and its parent is never pruned
@@ -3318,6 +3365,7 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
                     pass_n += 1ull << 32;  // (the high half: reused leaves)
                 }
             }
+            if constexpr (!kLeaf)
             if (k < N) {
                 unsigned long long limit;
                 const unsigned long long off =
@@ -3378,18 +3426,18 @@ void k_bnb_bound_refill(int k, const hvp_system* __restrict__ systems, int n_sys
 #else
                         code = ws.nd_code[dst][mine];
 #endif
-                        if (code & kPassFlag) {  // its parent's QP: finished at the next event
+                        if (!kLeaf && (code & kPassFlag)) {  // its parent's QP: finished at the next event
                             fail = (int)((code >> 56) & 127);
                             code &= kPassCode;
                             stage = RS_PASS;
                         } else {
 #if HVP_REFILL_NODE_BATCH
                             setup_node_batch<N>(q, tab, sys, role, params, C, ws, inst, code, k, nlo, nhi,
-                                                HVP_REFILL_CHILD_ONCE ? &nmask : nullptr);
+                                                HVP_REFILL_CHILD_ONCE && !kLeaf ? &nmask : nullptr);
 #else
                             setup_node<N>(q, tab[sys[inst]], C, ws, inst, role[inst],
                                           params + (size_t)inst * C.stride, code, k, ws.nd_lo[dst][mine],
-                                          ws.nd_hi[dst][mine], HVP_REFILL_CHILD_ONCE ? &nmask : nullptr);
+                                          ws.nd_hi[dst][mine], HVP_REFILL_CHILD_ONCE && !kLeaf ? &nmask : nullptr);
 #endif
                             stage = g.init(q) == hvp::GI_OK ? RS_SCAN : RS_FAIL;
                             fail = hvp::GI_FAIL_CHOL;
@@ -4254,22 +4302,43 @@ hipError_t node_records(hvp_handle* h, int B, Workspace& ws) {
 
 // one launch of the refill kernel over level k's list; which = 0: the level lists, 1: the dive list
 // (hvp_handle::ws_up).  The instantiation that stages the system tables in LDS when the handle's
-// systems fit its cap, else the one that reads them from global memory.
+// systems fit its cap, else the one that reads them from global memory; and, with `phases`, the
+// one of the level's phase (k_bnb_bound_refill: RP_LEAF at k == N, RP_UPPER at k + 1 < N; level
+// N - 1, and every level without `phases`, RP_ANY).
+#if HVP_REFILL_BYVAL
+template <int N, bool STAGE>
+void launch_refill_ph(hvp_handle* h, int grid, size_t lds, hipStream_t st, int k, const int32_t* sys,
+                      const int32_t* role, const double* params, int which, bool phases) {
+    constexpr int BS = kBnbBlock<N>;
+    if constexpr (kRefillPhLeaf<N, STAGE>) {
+        if (phases && k == N) {
+            hipLaunchKernelGGL((k_bnb_bound_refill<N, STAGE, RP_LEAF>), dim3(grid), dim3(BS), lds, st, k, h->d_sys,
+                               h->n_systems, sys, role, params, h->C, h->ws_up[which]);
+            return;
+        }
+    }
+    if constexpr (kRefillPhUpper<N, STAGE>) {
+        if (phases && k + 1 < N) {
+            hipLaunchKernelGGL((k_bnb_bound_refill<N, STAGE, RP_UPPER>), dim3(grid), dim3(BS), lds, st, k, h->d_sys,
+                               h->n_systems, sys, role, params, h->C, h->ws_up[which]);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_bnb_bound_refill<N, STAGE, RP_ANY>), dim3(grid), dim3(BS), lds, st, k, h->d_sys,
+                       h->n_systems, sys, role, params, h->C, h->ws_up[which]);
+}
+#endif
 template <int N>
 void launch_refill(hvp_handle* h, int grid, size_t lds, hipStream_t st, int k, const int32_t* sys,
-                   const int32_t* role, const double* params, int which) {
-    constexpr int BS = kBnbBlock<N>;
+                   const int32_t* role, const double* params, int which, bool phases) {
 #if HVP_REFILL_BYVAL
 #if HVP_REFILL_SYS_LDS
-    if (h->n_systems <= kRefillSysCap) {
-        hipLaunchKernelGGL((k_bnb_bound_refill<N, true>), dim3(grid), dim3(BS), lds, st, k, h->d_sys, h->n_systems,
-                           sys, role, params, h->C, h->ws_up[which]);
-        return;
-    }
+    if (h->n_systems <= kRefillSysCap) return launch_refill_ph<N, true>(h, grid, lds, st, k, sys, role, params, which, phases);
 #endif
-    hipLaunchKernelGGL((k_bnb_bound_refill<N, false>), dim3(grid), dim3(BS), lds, st, k, h->d_sys, h->n_systems, sys,
-                       role, params, h->C, h->ws_up[which]);
+    launch_refill_ph<N, false>(h, grid, lds, st, k, sys, role, params, which, phases);
 #else
+    constexpr int BS = kBnbBlock<N>;
+    (void)phases;
     hipLaunchKernelGGL(k_bnb_bound_refill<N>, dim3(grid), dim3(BS), lds, st, k, h->d_sys, sys, role, params, h->C,
                        h->d_ws + which, h->d_consts, h->ws_up[which]);
 #endif
@@ -4315,6 +4384,10 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
     const char* dr = std::getenv("HVP_DIVE_REUSE");
     ws.reuse = root_refill && !(dr && dr[0] == '0');
     h->last_reuse = ws.reuse != 0;
+    // the refill kernel's instantiation by the level's phase (launch_refill); HVP_REFILL_PHASES=0:
+    // every launch through the one kernel for all levels (A/B, tests)
+    const char* rp = std::getenv("HVP_REFILL_PHASES");
+    const bool phases = !(rp && rp[0] == '0');
     if (fused) {
         // the refill kernel's workspace descriptors ([0] the level lists, [1] the dive list in
         // place of level N's), uploaded when they change
@@ -4437,12 +4510,12 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
             // for each wave's slowest root + dive.  (root_refill: above.)
             if (root_refill) {
                 const int g_root = (int)std::min<long long>((B + BS - 1) / BS, (long long)h->n_cu * kRefillBlocksPerCu);
-                launch_refill<N>(h, g_root, lds, st, 0, sys, role, params, 0);
+                launch_refill<N>(h, g_root, lds, st, 0, sys, role, params, 0, phases);
                 HIP_TRY(hipGetLastError());
                 hipLaunchKernelGGL(k_bnb_dive_prep<N>, dim3(grid_for(B)), dim3(kBlock), 0, st, B, h->d_sys, sys, params,
                                    h->C, ws);
                 HIP_TRY(hipGetLastError());
-                launch_refill<N>(h, g_root, lds, st, N, sys, role, params, 1);
+                launch_refill<N>(h, g_root, lds, st, N, sys, role, params, 1, phases);
             } else {
                 // (one lane per instance, 1 wave per SIMD)
                 hipLaunchKernelGGL((k_bnb_root<N, false>), dim3((B + BS - 1) / BS), dim3(BS), lds, st, B, h->d_sys,
@@ -4499,7 +4572,7 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
                 // persistent waves: 2 blocks per CU, every wave refills its lanes until the level is done
                 const int g_refill = (int)std::min<long long>((h->ws.cap + BS - 1) / BS,
                                                               (long long)h->n_cu * kRefillBlocksPerCu);
-                launch_refill<N>(h, g_refill, lds, st, k, sys, role, params, 0);
+                launch_refill<N>(h, g_refill, lds, st, k, sys, role, params, 0, phases);
             }
         }
         HIP_TRY(hipGetLastError());

@@ -19,6 +19,7 @@ for n in 2 3 4 5 6 7 8 9 10 11 12 13 14 15 16; do
 done
 /opt/rocm/bin/hipcc $FLAGS $INC -c -o "$B/hvp_cent.o" csrc/hvp_cent.hip & pids+=($!)
 /opt/rocm/bin/hipcc $FLAGS $INC -c -o "$B/hvp_env.o" csrc/hvp_env.hip & pids+=($!)
+/opt/rocm/bin/hipcc $FLAGS $INC -c -o "$B/hvp_seq.o" csrc/hvp_seq.hip & pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "lib/libhvpsolve_$NAME.so" "$B"/hvp_kernels.o "$B"/hvp_lane_*.o "$B"/hvp_cent.o "$B"/hvp_env.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "lib/libhvpsolve_$NAME.so" "$B"/hvp_kernels.o "$B"/hvp_lane_*.o "$B"/hvp_cent.o "$B"/hvp_env.o "$B"/hvp_seq.o
 echo "lib/libhvpsolve_$NAME.so"

@@ -34,11 +34,25 @@ import sys
 
 
 def per_kernel(path: str) -> dict:
+    """short kernel name -> counter -> one value per launch.  The instantiations of one kernel
+    (k_bnb_bound_refill's phases) share the short name: their launches are one list."""
     acc = collections.defaultdict(lambda: collections.defaultdict(list))
     with open(path) as f:
         for r in csv.DictReader(f):
-            acc[r["Kernel_Name"]][r["Counter_Name"]].append(float(r["Counter_Value"]))
+            acc[short(r["Kernel_Name"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
     return acc
+
+
+def trace_rows(path: str) -> dict:
+    """short kernel name -> {avg_ms, calls} of a kernel-stats CSV; rows of the same short name are
+    merged: calls summed, the average weighted by calls."""
+    tot = collections.OrderedDict()
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            t = tot.setdefault(short(r["Name"]), [0.0, 0])
+            t[0] += float(r["AverageNs"]) * int(r["Calls"])
+            t[1] += int(r["Calls"])
+    return {k: {"avg_ms": (ns / calls if calls else 0.0) / 1e6, "calls": calls} for k, (ns, calls) in tot.items()}
 
 
 def short(name: str) -> str:
@@ -53,18 +67,13 @@ def short(name: str) -> str:
     return name[:48]
 
 
-def main() -> None:
-    src, rnd = sys.argv[1], sys.argv[2]
-    tag = sys.argv[3] if len(sys.argv) > 3 else None
+def summarize(src: str, rnd: str, tag: str | None = None, here: str | None = None) -> dict:
+    """Writes <here>/<rnd>[_<tag>]_{kernel_stats.csv,summary.json} (here: this directory) and returns the summary."""
     if tag:
         rnd = f"{rnd}_{tag}"
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = {}
-    with open(os.path.join(src, "trace", "run_kernel_stats.csv")) as f:
-        for r in csv.DictReader(f):
-            k = short(r["Name"])
-            out.setdefault(k, {})["avg_ms"] = float(r["AverageNs"]) / 1e6
-            out[k]["calls"] = int(r["Calls"])
+    if here is None:
+        here = os.path.dirname(os.path.abspath(__file__))
+    out = trace_rows(os.path.join(src, "trace", "run_kernel_stats.csv"))
     shutil.copy(os.path.join(src, "trace", "run_kernel_stats.csv"), os.path.join(here, f"{rnd}_kernel_stats.csv"))
     # extra workloads traced on their own (e.g. gadmm/): kernel stats kept as <round>_<name>_kernel_stats.csv
     extra = {}
@@ -73,15 +82,12 @@ def main() -> None:
         if name == "trace" or not os.path.exists(p):
             continue
         shutil.copy(p, os.path.join(here, f"{rnd}_{name}_kernel_stats.csv"))
-        with open(p) as f:
-            extra[name] = {short(r["Name"]): {"avg_ms": float(r["AverageNs"]) / 1e6, "calls": int(r["Calls"])}
-                           for r in csv.DictReader(f)}
+        extra[name] = trace_rows(p)
     for sub in ("fetch", "write", "f64", "occ", "mem"):
         p = os.path.join(src, sub, "run_counter_collection.csv")
         if not os.path.exists(p):
             continue
-        for name, ctr in per_kernel(p).items():
-            k = short(name)
+        for k, ctr in per_kernel(p).items():
             d = out.setdefault(k, {})
             for c, vals in ctr.items():
                 d[c] = sum(vals) / len(vals)
@@ -117,6 +123,11 @@ def main() -> None:
             "kernels": out, "workloads": extra}
     with open(os.path.join(here, f"{rnd}_summary.json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
+    return meta
+
+
+def main() -> None:
+    meta = summarize(sys.argv[1], sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
     print(json.dumps(meta, indent=1, sort_keys=True))
 
 
