@@ -155,10 +155,4 @@ struct hvp_handle {
     int nrec_slots = 0;         // slots allocated (nrec_want, halved until it fits the free HBM)
     unsigned long long nrec_epoch = 0;
     bool nrec_enable = true;  // hvp_set_node_records
-    // device copies of the workspace descriptors the refill kernel reads in its event code
-    // (hvp_lane.h k_bnb_bound_refill): [0] the level lists, [1] the dive list; re-uploaded when
-    // they change (a reserve, another bucket split)
-    hvp_detail::Workspace* d_ws = nullptr;
-    hvp_detail::Workspace ws_up[2];
-    bool ws_up_valid = false;
 };

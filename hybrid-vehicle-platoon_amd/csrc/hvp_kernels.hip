@@ -330,7 +330,6 @@ int hvp_create(hvp_handle** out, const hvp_problem* problem, const hvp_system* s
         hipMalloc(&h->g_counter, 8 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(&h->d_consts, sizeof(hvp::Consts)) != hipSuccess ||
         hipMemcpy(h->d_consts, &h->C, sizeof(hvp::Consts), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&h->d_ws, 2 * sizeof(hvp_detail::Workspace)) != hipSuccess ||
         hipMemset(h->g_counter, 0, 8 * sizeof(unsigned long long)) != hipSuccess ||
         !create_events(h->evb, 2 * (HVP_MAX_N + 1))) {
         hvp_destroy(h);
@@ -750,7 +749,6 @@ void hvp_destroy(hvp_handle* h) {
     if (h->nrec) (void)hipFree(h->nrec);
     if (h->nclaim) (void)hipFree(h->nclaim);
     if (h->d_consts) (void)hipFree(h->d_consts);
-    if (h->d_ws) (void)hipFree(h->d_ws);
     if (h->gadmm_redo) (void)hipFree(h->gadmm_redo);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);

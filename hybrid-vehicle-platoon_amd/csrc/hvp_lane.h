@@ -1467,9 +1467,6 @@ __device__ inline unsigned long long node_prio(const Workspace& ws, uint64_t cod
 // steps, its children's bucket).  Returns 1 when it wrote one.
 constexpr uint64_t kPassFlag = 1ull << 63;  // codes of N <= 8 steps use 32 bits
 constexpr uint64_t kPassCode = (1ull << 56) - 1;
-#ifndef HVP_REFILL_BYVAL
-#define HVP_REFILL_BYVAL 1  // (k_bnb_bound_refill's body; only the default one reads pass-through nodes)
-#endif
 template <bool CLAIM = false>
 __device__ inline int bnb_put_children(const Workspace& ws, int lv, unsigned long long off, unsigned long long limit,
                                         unsigned mask, int inst, const hvp_system& S, const hvp::Consts& C,
@@ -1481,10 +1478,7 @@ __device__ inline int bnb_put_children(const Workspace& ws, int lv, unsigned lon
         // them out of hvp_stats.n_candidates)
         if (off < limit) atomicAdd(&ws.counter[0], limit - off);
         bool placed = false;
-#ifndef HVP_SPILL
-#define HVP_SPILL 1
-#endif
-        if (HVP_SPILL && ws.split > 1) {
+        if (ws.split > 1) {
             const unsigned long long cap = (unsigned long long)ws.cap, seg = cap >> ws.split_shift;
             for (int j = 0; j < ws.split && !placed; ++j) {
                 const unsigned long long base = (unsigned long long)j * seg,
@@ -1512,7 +1506,7 @@ __device__ inline int bnb_put_children(const Workspace& ws, int lv, unsigned lon
         double a, b;
         hvp::bnb_child(S, C, lv - 1, lo, hi, r, &a, &b);
         uint64_t cc = hvp::code_with(code, lv - 1, r);
-        if (HVP_REFILL_BYVAL && ws.pass && pass >= 0 && nc == 1 && lo >= S.vlo[r] && hi <= S.vhi[r]) {
+        if (ws.pass && pass >= 0 && nc == 1 && lo >= S.vlo[r] && hi <= S.vhi[r]) {
             cc |= kPassFlag | ((uint64_t)(pass < 127 ? pass : 127) << 56);
             passed = 1;
         }
@@ -2511,21 +2505,6 @@ __global__ __launch_bounds__(kBnbBlock<N>) void k_lp_bound(int k, const hvp_syst
 // done -> write 64 results) ran at 2.73M against this kernel's 4.87M (profiles/r02q_*): with two
 // trip-loop levels the compiler's allocation spills ~3x more scratch traffic inside the trips.
 // Same results per node as k_bnb_bound (the node -> lane mapping does not matter).
-// where the refill kernel's event reads the workspace descriptor and the problem constants
-// (A/B builds): 1 = the by-value kernel arguments, 0 = the handle's device copies through
-// uniform_opaque pointers (the level index laundered too)
-// HVP_REFILL_BYVAL (default): round 3's kernel body -- the workspace descriptor and the problem
-// constants as by-value kernel arguments, the level list hoisted; 0: the variants below (measured
-// slower: 2.97-3.15 vs 2.68 ms of QP launches per C2 step, profiles/r04i_bench_*, r04j_bench_*)
-#ifndef HVP_REFILL_BYVAL
-#define HVP_REFILL_BYVAL 1
-#endif
-#ifndef HVP_REFILL_WS_ARG
-#define HVP_REFILL_WS_ARG 0
-#endif
-#ifndef HVP_REFILL_C_ARG
-#define HVP_REFILL_C_ARG 0
-#endif
 #ifndef HVP_REFILL_WAVES
 #define HVP_REFILL_WAVES 2
 #endif
@@ -2619,31 +2598,11 @@ __global__ __launch_bounds__(kBlock) void k_bnb_dive_prep(int B, const hvp_syste
     if (qp) atomicAdd(&ws.counter[3], (unsigned long long)qp);
 }
 
-// the node QP of instance inst from the per-instance part + the node's regions / relaxation
-template <int N, class Q>
-__device__ inline bool setup_node(Q& q, const hvp_system& S, const hvp::Consts& C, const Workspace& ws, int inst,
-                                  int rl, const double* prm, uint64_t code, int K, double rlo, double rhi,
-                                  unsigned* kmask = nullptr) {
-    constexpr int NT = N * (N + 1) / 2;
-    const double* o = static_cast<const double*>(__builtin_assume_aligned(ws.iq + (size_t)inst * kIqStride<N>, 128));
-    const bool ok = hvp::setup_scalars<N>(q, S, rl, prm[0], prm[1]);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) q.H[j] = o[j];
-#pragma unroll
-    for (int j = 0; j < N; ++j) q.f[j] = o[NT + j];
-#pragma unroll
-    for (int j = 0; j < N - 1; ++j) {
-        q.mem.set(hvp::F_HF, j, o[NT + N + j]);
-        q.mem.set(hvp::F_HB, j, o[NT + 2 * N - 1 + j]);
-    }
-    q.C0 = 0.0;  // not used by the active-set path (costs come from direct_cost)
-    hvp::setup_input<N>(q, S, C, code, K, rlo, rhi, kmask);
-    return ok;
-}
-
-// setup_node for the refill event, its loads issued together: the instance's system index, role
-// and x0 first, the ws.iq row behind them, and one wait for all (setup_node's caller waits for
-// sys[inst] to address the table, then for the role and x0, before the row is asked for).
+// the node QP of instance inst from the per-instance part + the node's regions / relaxation, for
+// the refill event.  Its loads are issued together: the instance's system index, role and x0
+// first, the ws.iq row behind them, and one wait for all (not one wait for sys[inst] to address
+// the table, one for the role and x0, and only then the row).  kmask: the regions the node can
+// take at step K (setup_input), the event's child set.
 template <int N, class Q>
 __device__ inline bool setup_node_batch(Q& q, const hvp_system* tab, const int32_t* sys, const int32_t* role,
                                         const double* params, const hvp::Consts& C, const Workspace& ws, int inst,
@@ -2674,7 +2633,7 @@ __device__ inline bool setup_node_batch(Q& q, const hvp_system* tab, const int32
         q.mem.set(hvp::F_HF, j, hf[j]);
         q.mem.set(hvp::F_HB, j, hb[j]);
     }
-    q.C0 = 0.0;
+    q.C0 = 0.0;  // not used by the active-set path (costs come from direct_cost)
     hvp::setup_input<N>(q, S, C, code, K, rlo, rhi, kmask);
     return ok;
 }
@@ -3054,106 +3013,63 @@ __device__ inline void gi_trip(Q& q, hvp::GiLane<N>& g, const hvp::Consts& C, in
 #endif
 }
 
-// A uniform pointer the compiler must treat as unknown at this point: loads through it cannot be
-// hoisted above it (k_bnb_bound_refill reads its event-only constants this way, so they occupy
-// scalar registers only inside the event instead of across the whole persistent loop).
-template <class T>
-__device__ inline const T* uniform_opaque(const T* p) {
-    asm volatile("" : "+s"(p));
-    return p;
-}
-
-// Persistent refill kernel.  Register discipline: the trip loop (gi_trip) keeps the lane QP and
-// the Goldfarb-Idnani state in VGPRs and only the trip constants (C.acc, C.dec, C.w of the kernel
-// argument) in SGPRs; everything the event needs -- the workspace descriptor (wsd), the rest of
-// the problem constants (cd: the handle's device copy of C), the level list's bucket counts -- is
-// loaded inside the event through uniform_opaque pointers.  (With both structures as kernel
-// arguments live across the loop, 128 SGPRs spilled into two VGPRs' lanes and 35 dwords of VGPRs
-// into scratch.)
+// Persistent refill kernel: where its data lives, and why (the measurements are DESIGN.md
+// section 4's dated entries; the alternatives are no longer in the source).
 //
-// System tables: the event's region loops (relax_step, bnb_child, bnb_put_children) and
+// Arguments.  The workspace descriptor and the problem constants are by-value kernel arguments and
+// the level list is hoisted above the loop.  Reading them inside the event through device copies
+// took the kernel off most of its scratch and was slower all the same (2.97-3.15 against 2.68 ms
+// of QP launches per step: every load through an opaque pointer is issued again after each store
+// of the event; DESIGN.md "Round 4: where the refill event reads its descriptors",
+// profiles/r04i_bench_*, r04j_bench_*).
+//
+// System tables.  The event's region loops (relax_step, bnb_child, bnb_put_children) and
 // direct_cost read hvp_system fields tens of times per node, each a dependent per-lane load
 // (systems[sys[inst]]).  STAGE: the block copies the handle's n_sys tables into LDS at entry and
 // the event indexes that copy by sys[inst] (a batch may mix systems).  At most kRefillSysCap
 // tables: at N = 5 the per-lane rows take 71,680 B of the 81,920 B a block may use with two
 // blocks per CU, and 8 tables are 6,144 B.  A handle with more systems runs the STAGE = false
-// instantiation, which reads them from global memory (launch_refill).
-// HVP_REFILL_SYS_LDS=0 builds only the global-memory instantiation (A/B).
-// HVP_REFILL_CHILD_ONCE: the node's child set is the mask its set-up's relax_step at step k
-// found, kept in a lane register until the write-back, instead of bnb_children's second pass
-// over the regions there (the same calls with the same arguments; 0: A/B).
-#ifndef HVP_REFILL_SYS_LDS
-#define HVP_REFILL_SYS_LDS 1
-#endif
-#ifndef HVP_REFILL_CHILD_ONCE
-#define HVP_REFILL_CHILD_ONCE 1
-#endif
-// The event's loads, batched (each 0: the code before, A/B):
-// HVP_REFILL_DC_BATCH: direct_cost loads the lane's whole parameter row before its step loop
-// (hvp_ipm.h, BATCH), for horizons up to kRefillDcBatchMaxN.
-// HVP_REFILL_INC_BATCH: the incumbent's key is fetched with that row instead of after the node's
-// write-back (needs DC_BATCH).
-// HVP_REFILL_NODE_BATCH: the claimed slot's four node fields are loaded together, then sys, role
-// and x0 together, instead of one after the other.
-#ifndef HVP_REFILL_DC_BATCH
-#define HVP_REFILL_DC_BATCH 1
-#endif
-#ifndef HVP_REFILL_INC_BATCH
-#define HVP_REFILL_INC_BATCH 1
-#endif
-#ifndef HVP_REFILL_NODE_BATCH
-#define HVP_REFILL_NODE_BATCH 1
-#endif
-constexpr int kRefillDcBatchMaxN = 8;
-template <int N>
-constexpr bool kRefillDcBatch = HVP_REFILL_DC_BATCH && N <= kRefillDcBatchMaxN;
+// instantiation, which reads them from global memory (launch_refill).  (DESIGN.md 2026-10-19,
+// profiles/r07a_refill_tables_ab.jsonl.)
+//
+// Child set.  A node's children are the mask its set-up's relax_step at step k found, kept in a
+// lane register (nmask) until the write-back: bnb_children's calls with the same arguments, made
+// once (profiles/r07a_refill_tables_stack_ab.jsonl).
+//
+// Loads in batches.  direct_cost loads the lane's whole parameter row before its step loop
+// (hvp_ipm.h, BATCH) and the incumbent's key with it; the claimed slot's four node fields are
+// loaded together, then sys, role, x0 and the ws.iq row together (setup_node_batch).  (DESIGN.md
+// 2026-10-20 "loads in batches", profiles/r07b_refill_event_ab.jsonl.)
 constexpr int kRefillSysCap = 8;
-// The block's copy of what is uniform over a launch and holds no pointer: the problem constants
-// (~95 dwords with dec[16] and acc[16]) and the hoisted level list, written to LDS once at entry
-// (before the one barrier) and read from there.  Together with the workspace descriptor's ~120
-// dwords the kernel arguments, live across the persistent loop, are twice the 102 SGPRs: the rest
-// sits in VGPR lanes (v_writelane / v_readlane, one dword at a time, 84 of them in the trip's
-// scan for C.dec[j], C.acc[j], C.w and the tolerances) and pushes lane state into scratch.  The
-// readers bind references to the __shared__ object itself, so the address space stays known after
-// inlining (ds_read, never flat_load), and LDS reads cannot alias the event's global stores.
-// uni_view() makes the object's offset opaque where it is called -- once per event, once per
-// trip -- so the loads stay there instead of being hoisted above the loop into registers again
-// (as LdsMem::refresh() does for the lane rows).
+// Uniform data.  The block's copy of what is uniform over a launch and holds no pointer: the
+// problem constants (~95 dwords with dec[16] and acc[16]) and the hoisted level list, written to
+// LDS once at entry (before the one barrier) and read from there by the event.  Together with the
+// workspace descriptor's ~120 dwords the kernel arguments, live across the persistent loop, are
+// twice the 102 SGPRs: the rest sits in VGPR lanes (v_writelane / v_readlane, one dword at a
+// time) and pushes lane state into scratch.  The readers bind references to the __shared__
+// object itself, so the address space stays known after inlining (ds_read, never flat_load), and
+// LDS reads cannot alias the event's global stores.  uni_view() makes the object's offset opaque
+// where it is called, once per event, so the loads stay there instead of being hoisted above the
+// loop into registers again (as LdsMem::refresh() does for the lane rows).
 // The descriptor itself stays a by-value argument: a pointer read back from LDS is a generic one
 // to the compiler (flat_load / flat_store / flat_atomic for every access of the event -- a cast
 // through the global address space is folded away, and a local copy with the casts is indexed by
 // the level's parity at run time, so it lands in scratch), where a kernel argument is known to
 // point to global memory.
-// HVP_REFILL_UNI_LDS: master switch; HVP_REFILL_UNI_EVENT: the event's reads (constants, level
-// list); HVP_REFILL_UNI_TRIP: the trips' Consts reads.  0: the by-value arguments, the code
-// before (A/B).  The trips keep the argument (default 0): with the event off it, the constants
-// the scan needs fit the scalar registers, and uniform values read from LDS land in VGPRs, which
-// the trip has none to spare (measured: event alone -5.1 %, both -4.0 %, trips alone -1.6 %,
-// profiles/r08a_refill_uniform_ab.jsonl).
-// HVP_REFILL_CLAIM_EARLY: the claim's atomic is issued at the top of the event (the free lanes
-// are known there, and whether the list is exhausted does not depend on the write-back) and
-// consumed after the write-back.  Claim order only decides which wave solves which node.
-#ifndef HVP_REFILL_UNI_LDS
-#define HVP_REFILL_UNI_LDS 1
-#endif
-#ifndef HVP_REFILL_UNI_TRIP
-#define HVP_REFILL_UNI_TRIP 0
-#endif
-#ifndef HVP_REFILL_UNI_EVENT
-#define HVP_REFILL_UNI_EVENT 1
-#endif
-#ifndef HVP_REFILL_CLAIM_EARLY
-#define HVP_REFILL_CLAIM_EARLY 0
-#endif
+// The trips read the constants from the argument: with the event off it, what the scan needs fits
+// the scalar registers, and uniform values read from LDS land in VGPRs, of which the trip has
+// none to spare (event alone -5.1 %, event and trips -4.0 %: DESIGN.md 2026-10-20 "from LDS",
+// profiles/r08a_refill_uniform_ab.jsonl, series 1).
+// The claim's atomic follows the write-back: issued at the top of the event and consumed after
+// it, it was 1.7-1.8 % slower in every run (the same entry and file, series 3).
 // The event reads the copy at the horizons where that takes the kernel off scratch (N >= 5: every
 // one of them holds less scratch per lane with it, profiles/r08a_refill_static.txt).  Below, the
 // arguments fit the registers, the copy only costs a few (N = 2: 162 -> 171 VGPRs, N = 2 and 4:
-// 36 B/lane of scratch that the code before does not have), and those horizons keep that code.
+// 36 B/lane of scratch that the by-value reads do not have): those horizons read the arguments,
+// take no LDS for the copy and no barrier for it.
 constexpr int kRefillUniMinN = 5;
 template <int N>
-constexpr bool kRefillUniEvent = HVP_REFILL_UNI_LDS && HVP_REFILL_UNI_EVENT && N >= kRefillUniMinN;
-template <int N>
-constexpr bool kRefillUniFill = HVP_REFILL_UNI_LDS && (kRefillUniEvent<N> || HVP_REFILL_UNI_TRIP);
+constexpr bool kRefillUniEvent = N >= kRefillUniMinN;
 struct RefillUni {
     hvp::Consts C;
     LevelList lvl;
@@ -3178,35 +3094,24 @@ __device__ inline const T& uni_view(const T& obj) {
 //   RP_UPPER  k + 1 < N, k at run time (levels 0..N-2): no leaf write-back (leaf_stat, task_y of a
 //             leaf, the incumbent's atomicMin, the redo list), no reuse block.
 // Level N - 1, the only one that enters the reuse block, runs RP_ANY.
-// The statements that remain are the same, in the same order: results are bit-equal.
-// HVP_REFILL_PH_LEAF / _UPPER: 0 sends that phase's launches through RP_ANY (the code before);
-// at run time HVP_REFILL_PHASES=0 does so for both (launch_bnb; tests, A/B).
-#ifndef HVP_REFILL_PH_LEAF
-#define HVP_REFILL_PH_LEAF 1
-#endif
-#ifndef HVP_REFILL_PH_UPPER
-#define HVP_REFILL_PH_UPPER 1
-#endif
-#ifndef HVP_REFILL_PH_PRELEAF
-#define HVP_REFILL_PH_PRELEAF 0  // (no instantiation of its own: level N - 1 keeps RP_ANY)
-#endif
+// The statements that remain are the same, in the same order: results are bit-equal.  At run time
+// HVP_REFILL_PHASES=0 sends every launch through RP_ANY (launch_bnb; tests, A/B).  Measured -4.3 %
+// per flagship step (DESIGN.md 2026-10-21 "by the level's phase", profiles/r11a_refill_phase_ab.jsonl);
+// an instantiation for level N - 1 or level 0 alone fails the static gate below (the same entry).
 enum { RP_ANY = 0, RP_LEAF = 1, RP_UPPER = 2 };
 // Which instantiations ship: those whose trip section (the stretch without a global access) has no
 // more instructions, scratch instructions or v_readlanes than RP_ANY's in the same build, at the
 // same waves per SIMD and LDS (profiles/r11a_refill_phase_static.txt, profiles/refill_static.py).
 // The register allocation of the trip moves with every edit of the event, although the trip's
-// source is the same in all three: a pair that misses keeps RP_ANY.  Bit N of [STAGE].
-constexpr int kRefillPhaseMaxN = HVP_MAX_N_ENUM;  // (the refill path's horizons)
+// source is the same in all three: a pair that misses keeps RP_ANY.  Bit N of [STAGE], N up to
+// HVP_MAX_N_ENUM (the refill path's horizons; the launchers of longer ones only test their bit).
 constexpr unsigned kRefillLeafOk[2] = {1u << 2 | 1u << 3 | 1u << 5 | 1u << 6 | 1u << 7 | 1u << 8,
                                        1u << 2 | 1u << 3 | 1u << 5 | 1u << 6 | 1u << 8};
 constexpr unsigned kRefillUpperOk[2] = {1u << 3 | 1u << 4, 1u << 3 | 1u << 4 | 1u << 5 | 1u << 8};
 template <int N, bool STAGE>
-constexpr bool kRefillPhLeaf = HVP_REFILL_PH_LEAF && N <= kRefillPhaseMaxN && ((kRefillLeafOk[STAGE] >> N) & 1u);
+constexpr bool kRefillPhLeaf = (kRefillLeafOk[STAGE] >> N) & 1u;
 template <int N, bool STAGE>
-constexpr bool kRefillPhUpper = HVP_REFILL_PH_UPPER && N <= kRefillPhaseMaxN && ((kRefillUpperOk[STAGE] >> N) & 1u);
-#if HVP_REFILL_BYVAL
-// (round 3's kernel body: the descriptor and the constants as by-value kernel arguments, the
-// level list hoisted)
+constexpr bool kRefillPhUpper = (kRefillUpperOk[STAGE] >> N) & 1u;
 template <int N, bool STAGE, int PH = RP_ANY>
 __global__ __launch_bounds__(kBnbBlock<N>) __attribute__((amdgpu_waves_per_eu(HVP_REFILL_WAVES)))
 void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n_sys, const int32_t* __restrict__ sys,
@@ -3220,7 +3125,7 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
     constexpr bool kUniEvent = kRefillUniEvent<N>;
     __shared__ RefillUni s_uni;  // (takes no LDS where nothing below uses it)
     const RefillUni& U = s_uni;
-    if constexpr (kRefillUniFill<N>) {
+    if constexpr (kUniEvent) {
         if (threadIdx.x == 0) {  // (from the arguments' scalar registers; the barrier is below)
             s_uni.C = C_arg;
             s_uni.lvl = level_list(ws_arg, k);
@@ -3238,10 +3143,10 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
         for (int i = threadIdx.x; i < nw; i += BS) dstw[i] = src[i];
         tab = s_sys;
     }
-    if (STAGE || kRefillUniFill<N>) __syncthreads();  // the only barrier: waves leave the loop at different times
+    if (STAGE || kUniEvent) __syncthreads();  // the only barrier: waves leave the loop at different times
     const int dst = k & 1;
     const Workspace& ws = ws_arg;
-    const LevelList lvl_arg = level_list(ws, k);  // (the code before; unused where the event reads the copy)
+    const LevelList lvl_arg = level_list(ws, k);  // (N < kRefillUniMinN; unused where the event reads the copy)
     const long long total_arg = lvl_arg.count();
     unsigned long long* const claim_arg = ws.lvl + (HVP_MAX_N + 1) + k;
     const int lane = threadIdx.x & 63;
@@ -3289,11 +3194,6 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
             const LevelList& lvl = kUniEvent ? E->lvl : lvl_arg;
             const long long total = kUniEvent ? E->total : total_arg;
             unsigned long long* const claim = kUniEvent ? ws.lvl + (HVP_MAX_N + 1) + k : claim_arg;
-#if HVP_REFILL_CLAIM_EARLY
-            unsigned long long claimed = 0;  // (the leader's lane holds the claim's first item)
-            if (!exhausted && lane == __ffsll((long long)free) - 1)
-                claimed = atomicAdd(claim, (unsigned long long)nfree);
-#endif
             unsigned cmask = 0;  // children of a finished bound node (k_bnb_expand's work, fused)
             double clb = 0.0;
             int csteps = 0;      // the finished node's active-set steps (its children's bucket)
@@ -3312,10 +3212,10 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
                 const bool ok = st == hvp::GI_OK;
                 // the incumbent's key, fetched with the cost's row (only leaves move it, and a launch
                 // of level k < N runs none; at k == N it is not read)
-                constexpr bool kInc = kRefillDcBatch<N> && HVP_REFILL_INC_BATCH && !kLeaf;
+                constexpr bool kInc = !kLeaf;
                 unsigned long long inck = 0;
                 if (kInc && !ok) inck = ws.inc[inst];
-                const double c = ok ? hvp::direct_cost<N, kRefillDcBatch<N>>(
+                const double c = ok ? hvp::direct_cost<N, true>(
                                           q, tab[sys[inst]], C, role[inst], params + (size_t)inst * C.stride, code,
                                           k, kInc ? ws.inc + inst : nullptr, &inck)
                                     : 0.0;
@@ -3335,13 +3235,8 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
                 // sees the value a separate expand kernel would
                 clb = ok ? c : -1e300;
                 if (k < N && !(ws.inst_flag[inst] & 2) &&
-                    !hvp::bnb_pruned(clb, kInc ? key_cost(inck) : inc_of(ws, inst))) {
-#if HVP_REFILL_CHILD_ONCE
-                    cmask = nmask;
-#else
-                    cmask = bnb_children(tab[sys[inst]], C, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
-#endif
-                }
+                    !hvp::bnb_pruned(clb, kInc ? key_cost(inck) : inc_of(ws, inst)))
+                    cmask = nmask;  // (the child set its set-up's relax_step found: bnb_children's)
                 }
             }
             if constexpr (PH == RP_ANY)
@@ -3383,14 +3278,8 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
             pf_wb += pf_w1 - pf_e0;
 #endif
             if (!exhausted) {
-#if HVP_REFILL_CLAIM_EARLY
-                const int leader = __ffsll((long long)free) - 1;
-                const unsigned long long base =
-                    ((unsigned long long)(unsigned)__shfl((int)(claimed >> 32), leader, 64) << 32) |
-                    (unsigned)__shfl((int)(claimed & 0xffffffffu), leader, 64);
-#else
+                // the claim, after the write-back (issued at the top of the event it was slower)
                 const unsigned long long base = wave_claim(claim, free, nfree, lane);
-#endif
 #ifdef HVP_REFILL_PROF
                 {
                     const unsigned long long bb = __builtin_amdgcn_readfirstlane((unsigned)base);
@@ -3402,7 +3291,6 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
                 const long long mc = (long long)base + wave_rank(free);
                 const long long mine = lvl.slot(mc);
                 if (stage == RS_IDLE && mc < total) {
-#if HVP_REFILL_NODE_BATCH
                     // the slot's four fields together (a dead slot's other three are allocated
                     // and not looked at)
                     int ninst = ws.nd_inst[dst][mine];
@@ -3413,32 +3301,19 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
                     hvp::pin_value(nlo);
                     hvp::pin_value(nhi);
                     inst = ninst;
-#else
-                    inst = ws.nd_inst[dst][mine];
-#endif
                     if (inst < 0) {  // dead slot of an overflowed reservation
                         if (k == N) ws.leaf_stat[mine] = HVP_OVERFLOW;
                         else ws.nd_lb[dst][mine] = 1e300;
                     } else {
                         t = mine;
-#if HVP_REFILL_NODE_BATCH
                         code = ncode;
-#else
-                        code = ws.nd_code[dst][mine];
-#endif
                         if (!kLeaf && (code & kPassFlag)) {  // its parent's QP: finished at the next event
                             fail = (int)((code >> 56) & 127);
                             code &= kPassCode;
                             stage = RS_PASS;
                         } else {
-#if HVP_REFILL_NODE_BATCH
                             setup_node_batch<N>(q, tab, sys, role, params, C, ws, inst, code, k, nlo, nhi,
-                                                HVP_REFILL_CHILD_ONCE && !kLeaf ? &nmask : nullptr);
-#else
-                            setup_node<N>(q, tab[sys[inst]], C, ws, inst, role[inst],
-                                          params + (size_t)inst * C.stride, code, k, ws.nd_lo[dst][mine],
-                                          ws.nd_hi[dst][mine], HVP_REFILL_CHILD_ONCE && !kLeaf ? &nmask : nullptr);
-#endif
+                                                !kLeaf ? &nmask : nullptr);
                             stage = g.init(q) == hvp::GI_OK ? RS_SCAN : RS_FAIL;
                             fail = hvp::GI_FAIL_CHOL;
                         }
@@ -3458,11 +3333,9 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
         unsigned long long pf_dscan = 0, pf_dstep = 0;
 #endif
         if (stage == RS_SCAN || stage == RS_STEP) {
-#if HVP_REFILL_UNI_LDS && HVP_REFILL_UNI_TRIP
-            const hvp::Consts& Ct = uni_view(U.C);
-#else
+            // the trip reads the argument, not the copy.  (Through this reference: with C_arg
+            // named in the call the same code comes out with a few instructions in another order.)
             const hvp::Consts& Ct = C_arg;
-#endif
 #ifdef HVP_REFILL_PROF
             gi_trip<N>(q, g, Ct, stage, fail, &pf_dscan, &pf_dstep);
 #else
@@ -3504,166 +3377,6 @@ void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, int n
     }
 #endif
 }
-#else
-template <int N>
-__global__ __launch_bounds__(kBnbBlock<N>) __attribute__((amdgpu_waves_per_eu(HVP_REFILL_WAVES)))
-void k_bnb_bound_refill(int k_arg, const hvp_system* __restrict__ systems, const int32_t* __restrict__ sys,
-                        const int32_t* __restrict__ role, const double* __restrict__ params, hvp::Consts C,
-                        const Workspace* __restrict__ wsd, const hvp::Consts* __restrict__ cd, Workspace wsv) {
-    (void)wsd, (void)cd;
-    constexpr int BS = kBnbBlock<N>;
-    static_assert(N <= HVP_MAX_N_ENUM, "lane refill is the N <= 8 path");
-    (void)wsv;
-    const int lane = threadIdx.x & 63;
-    hvp::LaneQp<N, LdsMem<N, BS>> q;
-    q.mem.lane = threadIdx.x;
-    hvp::GiLane<N> g;
-    long long t = -1;  // node of the lane
-    int inst = 0, stage = RS_IDLE, fail = 0;
-    uint64_t code = 0;
-    bool exhausted = false;
-    unsigned iter_sum = 0;
-#ifdef HVP_REFILL_PROF  // diagnostics build: event / trip cycles and busy lane-trips per wave
-    unsigned long long pf_ev = 0, pf_all = 0, pf_busy = 0, pf_trips = 0, pf_wb = 0, pf_cl = 0, pf_dc = 0, pf_rs = 0;
-    const unsigned long long pf_t0 = __builtin_amdgcn_s_memtime();
-    int pf_mine = 0, pf_gen = 0;
-#endif
-    for (;;) {
-        const bool done = stage >= RS_FAIL;
-        const unsigned long long free = __ballot(stage == RS_IDLE || done);
-        const int nfree = __popcll(free);
-#ifdef HVP_REFILL_PROF
-        const unsigned long long pf_e0 = __builtin_amdgcn_s_memtime();
-        const bool pf_event = nfree >= kRefillMin || nfree == 64;
-        pf_busy += (unsigned long long)(64 - nfree);
-        pf_trips += 1;
-        if (pf_event) {
-            if (done) atomicAdd(&g_pf_hist[pf_mine < 63 ? pf_mine : 63], 1ull);
-            if (lane == 0) atomicAdd(&g_pf_hist[64 + (pf_gen < 63 ? pf_gen : 63)], 1ull);
-            pf_gen = 0;
-            pf_mine = 0;
-        }
-        ++pf_gen;
-        if (stage == RS_SCAN || stage == RS_STEP) ++pf_mine;
-#endif
-        if (nfree >= kRefillMin || nfree == 64) {
-            // ---- event: write the finished lanes' results, then refill every free lane
-#if HVP_REFILL_WS_ARG
-            const Workspace& ws = wsv;
-#else
-            const Workspace& ws = *uniform_opaque(wsd);
-#endif
-#if HVP_REFILL_C_ARG
-            const hvp::Consts& Ce = C;
-            const int k = k_arg;
-#else
-            const hvp::Consts& Ce = *uniform_opaque(cd);
-            // the level, opaque here: the per-step tests on it (k < K in the QP set-up and the
-            // direct cost) are evaluated inside the event, not hoisted as spilled lane masks
-            int k = k_arg;
-            asm volatile("" : "+s"(k));
-#endif
-            const int dst = k & 1;
-            unsigned cmask = 0;  // children of a finished bound node (k_bnb_expand's work, fused)
-            double clb = 0.0;
-            if (done) {
-                const int st = stage == RS_OPT ? g.verify(Ce, nullptr) : fail;
-                const bool ok = st == hvp::GI_OK;
-                const double c = ok ? hvp::direct_cost<N>(q, systems[sys[inst]], Ce, role[inst],
-                                                          params + (size_t)inst * Ce.stride, code, k)
-                                    : 0.0;
-                iter_sum += (unsigned)g.iter;
-#ifdef HVP_REFILL_PROF
-                {
-                    const double cc = __builtin_amdgcn_readfirstlane(__double_as_longlong(c) & 0xffffffff);
-                    (void)cc;
-                    pf_dc += __builtin_amdgcn_s_memtime() - pf_e0;
-                }
-#endif
-                bnb_node_done<N>(k, t, inst, ok, g.iter, c, q.y, Ce, ws);
-                stage = RS_IDLE;
-                // the incumbent only changes at the leaves (level N): below N this pruning test
-                // sees the value a separate expand kernel would
-                clb = ok ? c : -1e300;
-                if (k < N && !(ws.inst_flag[inst] & 2) && !hvp::bnb_pruned(clb, inc_of(ws, inst)))
-                    cmask = bnb_children(systems[sys[inst]], Ce, k, ws.nd_lo[dst][t], ws.nd_hi[dst][t]);
-            }
-            if (k < N) {
-                unsigned long long limit;
-                const unsigned long long off =
-                    split_reserve(ws, k + 1, __popc(cmask), done ? g.iter : 0, lane, limit);
-                if (cmask)
-                    bnb_put_children(ws, k + 1, off, limit, cmask, inst, systems[sys[inst]], Ce, code,
-                                     ws.nd_lo[dst][t], ws.nd_hi[dst][t], clb);
-#ifdef HVP_REFILL_PROF
-                pf_rs += __builtin_amdgcn_s_memtime() - pf_e0;
-#endif
-            }
-            if (exhausted && nfree == 64) break;
-#ifdef HVP_REFILL_PROF
-            const unsigned long long pf_w1 = __builtin_amdgcn_s_memtime();
-            pf_wb += pf_w1 - pf_e0;
-#endif
-            if (!exhausted) {
-                // this level's list (its bucket counts are final: this launch writes level k + 1)
-                const LevelList lvl = level_list(ws, k);
-                const long long total = lvl.count();
-                const unsigned long long base = wave_claim(ws.lvl + (HVP_MAX_N + 1) + k, free, nfree, lane);
-#ifdef HVP_REFILL_PROF
-                {
-                    const unsigned long long bb = __builtin_amdgcn_readfirstlane((unsigned)base);
-                    (void)bb;
-                    pf_cl += __builtin_amdgcn_s_memtime() - pf_w1;
-                }
-#endif
-                if (base + nfree >= (unsigned long long)total) exhausted = true;
-                const long long mc = (long long)base + wave_rank(free);
-                const long long mine = lvl.slot(mc);
-                if (stage == RS_IDLE && mc < total) {
-                    inst = ws.nd_inst[dst][mine];
-                    if (inst < 0) {  // dead slot of an overflowed reservation
-                        if (k == N) ws.leaf_stat[mine] = HVP_OVERFLOW;
-                        else ws.nd_lb[dst][mine] = 1e300;
-                    } else {
-                        t = mine;
-                        code = ws.nd_code[dst][mine];
-                        setup_node<N>(q, systems[sys[inst]], Ce, ws, inst, role[inst], params + (size_t)inst * Ce.stride,
-                                      code, k, ws.nd_lo[dst][mine], ws.nd_hi[dst][mine]);
-                        stage = g.init(q) == hvp::GI_OK ? RS_SCAN : RS_FAIL;
-                        fail = hvp::GI_FAIL_CHOL;
-                    }
-                }
-            }
-        }
-#ifdef HVP_REFILL_PROF
-        if (pf_event) pf_ev += __builtin_amdgcn_s_memtime() - pf_e0;
-#endif
-        if (stage == RS_SCAN || stage == RS_STEP) gi_trip<N>(q, g, C, stage, fail);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) iter_sum += __shfl_down(iter_sum, off, 64);
-#if HVP_REFILL_WS_ARG
-    const Workspace& ws = wsv;
-#else
-    const Workspace& ws = *uniform_opaque(wsd);
-#endif
-    if (lane == 0 && iter_sum) atomicAdd(&ws.counter[1], (unsigned long long)iter_sum);
-#ifdef HVP_REFILL_PROF
-    pf_all = __builtin_amdgcn_s_memtime() - pf_t0;
-    if (lane == 0) {  // the claim slots of levels > N are free (prof builds need N <= 8)
-        unsigned long long* pf = ws.lvl + 2 * (HVP_MAX_N + 1) - 8;
-        atomicAdd(&pf[0], pf_ev);
-        atomicAdd(&pf[1], pf_all);
-        atomicAdd(&pf[2], pf_busy);
-        atomicAdd(&pf[3], pf_trips);
-        atomicAdd(&pf[4], pf_wb);
-        atomicAdd(&pf[5], pf_cl);
-        atomicAdd(&pf[6], pf_dc);
-        atomicAdd(&pf[7], pf_rs);
-    }
-#endif
-}
-#endif
 
 // Leaves whose active-set solve failed its verification (degenerate vertices, e.g. the
 // position box at p_max): re-solved by the interior-point method on the full row set
@@ -4300,48 +4013,57 @@ hipError_t node_records(hvp_handle* h, int B, Workspace& ws) {
     return hipSuccess;
 }
 
-// one launch of the refill kernel over level k's list; which = 0: the level lists, 1: the dive list
-// (hvp_handle::ws_up).  The instantiation that stages the system tables in LDS when the handle's
-// systems fit its cap, else the one that reads them from global memory; and, with `phases`, the
-// one of the level's phase (k_bnb_bound_refill: RP_LEAF at k == N, RP_UPPER at k + 1 < N; level
-// N - 1, and every level without `phases`, RP_ANY).
-#if HVP_REFILL_BYVAL
+// The descriptor of the dive list as a level-N list: ws with the dive's arrays, counts and claims
+// in place of level N's, one bucket of `cap` slots (launch_bnb: the quadratic and the LP search).
+inline Workspace dive_list_ws(const Workspace& ws, int N, long long cap) {
+    Workspace wd = ws;
+    wd.nd_inst[N & 1] = ws.dv_inst;
+    wd.nd_code[N & 1] = ws.dv_code;
+    wd.nd_lo[N & 1] = ws.dv_lo;
+    wd.nd_hi[N & 1] = ws.dv_hi;
+    wd.nd_lb[N & 1] = ws.dv_lb;
+    wd.leaf_stat = ws.dv_stat;
+    wd.task_y = ws.dv_y;
+    wd.redo = ws.dv_redo;
+    wd.lvl = ws.dv_lvl;
+    wd.counter = ws.dv_counter;
+    wd.cap = cap;
+    wd.split = 1;
+    wd.split_shift = 0;
+    return wd;
+}
+
+// one launch of the refill kernel over level k's list of `ws` (the level lists, or dive_list_ws).
+// The instantiation that stages the system tables in LDS when the handle's systems fit its cap,
+// else the one that reads them from global memory; and, with `phases`, the one of the level's
+// phase (k_bnb_bound_refill: RP_LEAF at k == N, RP_UPPER at k + 1 < N; level N - 1, and every
+// level without `phases`, RP_ANY).
 template <int N, bool STAGE>
 void launch_refill_ph(hvp_handle* h, int grid, size_t lds, hipStream_t st, int k, const int32_t* sys,
-                      const int32_t* role, const double* params, int which, bool phases) {
+                      const int32_t* role, const double* params, const Workspace& ws, bool phases) {
     constexpr int BS = kBnbBlock<N>;
     if constexpr (kRefillPhLeaf<N, STAGE>) {
         if (phases && k == N) {
             hipLaunchKernelGGL((k_bnb_bound_refill<N, STAGE, RP_LEAF>), dim3(grid), dim3(BS), lds, st, k, h->d_sys,
-                               h->n_systems, sys, role, params, h->C, h->ws_up[which]);
+                               h->n_systems, sys, role, params, h->C, ws);
             return;
         }
     }
     if constexpr (kRefillPhUpper<N, STAGE>) {
         if (phases && k + 1 < N) {
             hipLaunchKernelGGL((k_bnb_bound_refill<N, STAGE, RP_UPPER>), dim3(grid), dim3(BS), lds, st, k, h->d_sys,
-                               h->n_systems, sys, role, params, h->C, h->ws_up[which]);
+                               h->n_systems, sys, role, params, h->C, ws);
             return;
         }
     }
     hipLaunchKernelGGL((k_bnb_bound_refill<N, STAGE, RP_ANY>), dim3(grid), dim3(BS), lds, st, k, h->d_sys,
-                       h->n_systems, sys, role, params, h->C, h->ws_up[which]);
+                       h->n_systems, sys, role, params, h->C, ws);
 }
-#endif
 template <int N>
 void launch_refill(hvp_handle* h, int grid, size_t lds, hipStream_t st, int k, const int32_t* sys,
-                   const int32_t* role, const double* params, int which, bool phases) {
-#if HVP_REFILL_BYVAL
-#if HVP_REFILL_SYS_LDS
-    if (h->n_systems <= kRefillSysCap) return launch_refill_ph<N, true>(h, grid, lds, st, k, sys, role, params, which, phases);
-#endif
-    launch_refill_ph<N, false>(h, grid, lds, st, k, sys, role, params, which, phases);
-#else
-    constexpr int BS = kBnbBlock<N>;
-    (void)phases;
-    hipLaunchKernelGGL(k_bnb_bound_refill<N>, dim3(grid), dim3(BS), lds, st, k, h->d_sys, sys, role, params, h->C,
-                       h->d_ws + which, h->d_consts, h->ws_up[which]);
-#endif
+                   const int32_t* role, const double* params, const Workspace& ws, bool phases) {
+    if (h->n_systems <= kRefillSysCap) return launch_refill_ph<N, true>(h, grid, lds, st, k, sys, role, params, ws, phases);
+    launch_refill_ph<N, false>(h, grid, lds, st, k, sys, role, params, ws, phases);
 }
 
 template <int N>
@@ -4388,31 +4110,6 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
     // every launch through the one kernel for all levels (A/B, tests)
     const char* rp = std::getenv("HVP_REFILL_PHASES");
     const bool phases = !(rp && rp[0] == '0');
-    if (fused) {
-        // the refill kernel's workspace descriptors ([0] the level lists, [1] the dive list in
-        // place of level N's), uploaded when they change
-        Workspace up[2] = {ws, ws};
-        Workspace& wd = up[1];
-        wd.nd_inst[N & 1] = ws.dv_inst;
-        wd.nd_code[N & 1] = ws.dv_code;
-        wd.nd_lo[N & 1] = ws.dv_lo;
-        wd.nd_hi[N & 1] = ws.dv_hi;
-        wd.nd_lb[N & 1] = ws.dv_lb;
-        wd.leaf_stat = ws.dv_stat;
-        wd.task_y = ws.dv_y;
-        wd.redo = ws.dv_redo;
-        wd.lvl = ws.dv_lvl;
-        wd.counter = ws.dv_counter;
-        wd.cap = ws.max_batch;
-        wd.split = 1;
-        wd.split_shift = 0;
-        if (!h->ws_up_valid || std::memcmp(up, h->ws_up, sizeof(up)) != 0) {
-            HIP_TRY(hipDeviceSynchronize());  // a solve in flight may still read the old ones
-            HIP_TRY(hipMemcpy(h->d_ws, up, sizeof(up), hipMemcpyHostToDevice));
-            std::memcpy(h->ws_up, up, sizeof(up));
-            h->ws_up_valid = true;
-        }
-    }
     HIP_TRY(hipMemsetAsync(ws.counter, 0, 8 * sizeof(unsigned long long), st));
     HIP_TRY(hipMemsetAsync(ws.lvl, 0, (2 + kMaxBuckets) * (HVP_MAX_N + 1) * sizeof(unsigned long long), st));  // + claims, buckets
     if (ws.dv_counter) HIP_TRY(hipMemsetAsync(ws.dv_counter, 0, 8 * sizeof(unsigned long long), st));
@@ -4442,18 +4139,7 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
             const char* lrr = std::getenv("HVP_LP_ROOT_REFILL");
             const bool lp_root_refill = lp_refill > 0 && !(lrr && lrr[0] == '0') && ws.dv_mem;
             if (lp_root_refill) {
-                Workspace wd = ws;  // the dive list in place of level N's (its leaf arrays, counts, claims)
-                wd.nd_inst[N & 1] = ws.dv_inst;
-                wd.nd_code[N & 1] = ws.dv_code;
-                wd.nd_lo[N & 1] = ws.dv_lo;
-                wd.nd_hi[N & 1] = ws.dv_hi;
-                wd.nd_lb[N & 1] = ws.dv_lb;
-                wd.leaf_stat = ws.dv_stat;
-                wd.task_y = ws.dv_y;
-                wd.redo = ws.dv_redo;
-                wd.lvl = ws.dv_lvl;
-                wd.counter = ws.dv_counter;
-                wd.cap = 3 * ws.max_batch;
+                const Workspace wd = dive_list_ws(ws, N, 3LL * ws.max_batch);
                 hipLaunchKernelGGL(k_lp_root_init<N>, dim3(grid_for(B)), dim3(kBlock), 0, st, B, h->d_sys, sys, params,
                                    h->C, ws);
                 HIP_TRY(hipGetLastError());
@@ -4510,12 +4196,12 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
             // for each wave's slowest root + dive.  (root_refill: above.)
             if (root_refill) {
                 const int g_root = (int)std::min<long long>((B + BS - 1) / BS, (long long)h->n_cu * kRefillBlocksPerCu);
-                launch_refill<N>(h, g_root, lds, st, 0, sys, role, params, 0, phases);
+                launch_refill<N>(h, g_root, lds, st, 0, sys, role, params, ws, phases);
                 HIP_TRY(hipGetLastError());
                 hipLaunchKernelGGL(k_bnb_dive_prep<N>, dim3(grid_for(B)), dim3(kBlock), 0, st, B, h->d_sys, sys, params,
                                    h->C, ws);
                 HIP_TRY(hipGetLastError());
-                launch_refill<N>(h, g_root, lds, st, N, sys, role, params, 1, phases);
+                launch_refill<N>(h, g_root, lds, st, N, sys, role, params, dive_list_ws(ws, N, ws.max_batch), phases);
             } else {
                 // (one lane per instance, 1 wave per SIMD)
                 hipLaunchKernelGGL((k_bnb_root<N, false>), dim3((B + BS - 1) / BS), dim3(BS), lds, st, B, h->d_sys,
@@ -4572,7 +4258,7 @@ int launch_bnb(hvp_handle* h, int B, const int32_t* sys, const int32_t* role, co
                 // persistent waves: 2 blocks per CU, every wave refills its lanes until the level is done
                 const int g_refill = (int)std::min<long long>((h->ws.cap + BS - 1) / BS,
                                                               (long long)h->n_cu * kRefillBlocksPerCu);
-                launch_refill<N>(h, g_refill, lds, st, k, sys, role, params, 0, phases);
+                launch_refill<N>(h, g_refill, lds, st, k, sys, role, params, ws, phases);
             }
         }
         HIP_TRY(hipGetLastError());

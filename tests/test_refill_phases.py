@@ -329,6 +329,56 @@ def test_two_handles_alternating_on_two_streams(gpu_available, monkeypatch):
             assert np.array_equal(out[k].cpu().numpy(), getattr(alone[i], k)), (i, k)
 
 
+@gpu
+def test_one_handle_through_changing_descriptors(gpu_available, monkeypatch):
+    """The refill kernel takes its workspace descriptor by value, built per solve (launch_bnb,
+    dive_list_ws): nothing of an earlier solve's descriptor may reach a later one.  N = 5, 70
+    mixed-role instances (a full wave and a partial one), one system, one handle: a default solve;
+    one with HVP_SPLIT_LEVELS=1 (another level-list descriptor: one bucket per level); then
+    reserve(4 * B), which raises max_batch past the handle's, so hvp_reserve frees every workspace
+    array and the dive list and allocates them again at four times the size (the capacity and the
+    dive list's capacity change with it: both descriptors differ whatever addresses come back);
+    then a default solve again.  The first and the last solve are equal bit by bit with the same
+    counts (this module's three; n_spilled is printed), and all three are the host build's."""
+    import torch
+
+    from hvp import tables
+    from hvp.solver import BatchSolver
+
+    N, B = 5, 70
+    params, roles = _mixed_inputs(N)
+    sys_idx = np.zeros(B, np.int32)
+    dev = torch.device("cuda", 0)
+    ts, tr, tp = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (sys_idx, roles[:B], params[:B]))
+
+    def solve(s):
+        out = s.solve_device(ts, tr, tp)
+        torch.cuda.synchronize()
+        return {k: v.clone() for k, v in out.items()}, _stats(s)
+
+    monkeypatch.delenv("HVP_SPLIT_LEVELS", raising=False)
+    s = BatchSolver(tables.problem(N), [_gear_pwa(800.0)])
+    try:
+        first, st_first = solve(s)
+        cap_first = int(s.stats().capacity)
+        monkeypatch.setenv("HVP_SPLIT_LEVELS", "1")
+        one_list, st_one = solve(s)
+        monkeypatch.delenv("HVP_SPLIT_LEVELS")
+        s.reserve(4 * B)
+        last, st_last = solve(s)
+        cap_last = int(s.stats().capacity)
+    finally:
+        s.close()
+    print(f"capacity {cap_first} -> {cap_last}; (n_candidates, qp_iterations, n_fallback, n_spilled) {st_first} first, "
+          f"{st_one} one list, {st_last} last")
+    assert cap_last > cap_first, "reserve(4 * B) must have reallocated the workspace"
+    _same_outputs(first, last)
+    assert st_first[:3] == st_last[:3]
+    ref = {k: v[:B] for k, v in _mixed_hostref(N, 1).items()}
+    for out in (first, one_list, last):
+        _check_against_hostref(_as_result(out), ref)
+
+
 def _summarize():
     spec = importlib.util.spec_from_file_location("hvp_profiles_summarize", os.path.join(ROOT, "profiles", "summarize.py"))
     mod = importlib.util.module_from_spec(spec)
