@@ -28,14 +28,41 @@
 #include "hvp_gi.h"
 #include "hvp_ipm.h"
 
+// HVP_CENT_EVENT (csrc/hvp_event.hip only): the local problem of the event-based controller
+// (fleet_event_based.py LocalMpc) -- a sub-platoon of m <= 3 vehicles with the fixed trajectories
+// of the vehicles two places away at either end (Inst::xf2 / xb2), a leader term on any local
+// vehicle or none (Inst::L = -1) and a tenth row slot for the back boundary's soft row.  Every
+// addition sits behind the flag and in an inline namespace of its own, so the centralised unit
+// compiles exactly the code it did without it.
+#ifndef HVP_CENT_EVENT
+#define HVP_CENT_EVENT 0
+#endif
+
 namespace hvp {
 namespace cent {
+#if HVP_CENT_EVENT
+inline namespace ev {
+#endif
 
 constexpr int W = 64;
 constexpr int kMaxV = 64;     // one lane per velocity variable
 constexpr int kMaxVeh = 16;
+#if HVP_CENT_EVENT
+constexpr int ROWS = 10;      // rows per lane (9: the back boundary's soft row)
+#else
 constexpr int ROWS = 9;       // rows per lane
+#endif
 constexpr int REV = 1 << 10;  // reversed copy of a saturated soft row
+// soft rows of a lane and their bits in its saturation mask
+#if HVP_CENT_EVENT
+__device__ inline bool soft_row(int rr) { return rr >= 8; }
+__device__ inline unsigned sat_bit(int rr) { return 1u << (rr - 8); }
+constexpr unsigned kSatMask = 3u;
+#else
+__device__ inline bool soft_row(int rr) { return rr == 8; }
+__device__ inline unsigned sat_bit(int) { return 1u; }
+constexpr unsigned kSatMask = 1u;
+#endif
 
 // LDS carve of one wave: J, R (V x (V+1), row stride V + 1), a 64-entry vector and the
 // min_1_norm LP's row-descriptor buffer (64 rows x 10 doubles, hvp_cent_l1.h)
@@ -211,6 +238,10 @@ struct Inst {
     const double* x0;           // [2n] (p0, v0) per vehicle
     const double* xl;           // leader_x (2, N+1)
     int debug;                  // HVP_CENT_DEBUG: printf diagnostics of failing QPs
+#if HVP_CENT_EVENT
+    const double* xf2;          // (2, N+1) fixed trajectory in front of vehicle 0, or null
+    const double* xb2;          // (2, N+1) fixed trajectory behind vehicle n-1, or null
+#endif
 };
 
 struct Lane {
@@ -222,6 +253,10 @@ struct Lane {
     bool ucost;     // step a carries its input cost (fixed, or relaxed in a virtual region)
     int sf;       // 0 none, 1 pair row with vehicle i-1, 2 leader row w.r.t. x_ref
     double sfd;   // SF row: s_i(y) <= sfd with s = p_{i,a+1} (- p_{i-1,a+1})  (constants folded)
+#if HVP_CENT_EVENT
+    bool sb;      // row 9: the back boundary's soft row  -ts cum <= sbd  (p_b2 <= p - d_safe + s)
+    double sbd;
+#endif
     double y, f;
 };
 
@@ -259,6 +294,18 @@ __device__ inline Forms forms(const Consts& C, const Inst& I, int i) {
         F.Wpv += qpv;
         F.Wvv += qvv;
     }
+#if HVP_CENT_EVENT
+    if (i == 0 && I.xf2) {  // follower of the fixed x_f2 (fleet_event_based.py:176-185)
+        F.Wpp += qpp;
+        F.Wpv += qpp * t0 + qpv;
+        F.Wvv += qpp * t0 * t0 + 2.0 * qpv * t0 + qvv;
+    }
+    if (i == I.n - 1 && I.xb2) {  // predecessor of the fixed x_b2 (:199-210)
+        F.Wpp += qpp;
+        F.Wpv += qpv;
+        F.Wvv += qvv;
+    }
+#endif
     F.Cpp = -qpp;
     F.Cpv = -qpv;
     F.Cvp = -(qpp * t0 + qpv);
@@ -286,6 +333,19 @@ __device__ inline void lin(const Consts& C, const Inst& I, int i, int k, double&
         lp -= d0 * qpp;
         lv -= d0 * qpv;
     }
+#if HVP_CENT_EVENT
+    if (i == 0 && I.xf2) {  // e = (p + t0 v + d0 - p_f2, v - v_f2)
+        const double r0 = d0 - I.xf2[k], r1 = -I.xf2[I.N + 1 + k];
+        const double a0 = qpp * r0 + qpv * r1, a1 = qpv * r0 + qvv * r1;
+        lp += a0;
+        lv += t0 * a0 + a1;
+    }
+    if (i == I.n - 1 && I.xb2) {  // e = (p_b2 + t0 v_b2 + d0 - p, v_b2 - v): the spacing is data
+        const double r0 = -(I.xb2[k] + t0 * I.xb2[I.N + 1 + k] + d0), r1 = -I.xb2[I.N + 1 + k];
+        lp += qpp * r0 + qpv * r1;
+        lv += qpv * r0 + qvv * r1;
+    }
+#endif
 }
 
 // Lane data and Hessian row t (into LDS J) for the assignment ci (region code of the lane's
@@ -377,7 +437,17 @@ __device__ inline bool setup(Lane& L, const Lds& S_lds, const Consts& C, const I
             L.sf = 2;
             L.sfd = I.xl[a + 1] - C.d_safe - L.P1;
         }
+#if HVP_CENT_EVENT
+        else if (I.xf2) {  // p_f1 <= p_f2 - d_safe + s_f2 (:268-275)
+            L.sf = 2;
+            L.sfd = I.xf2[a + 1] - C.d_safe - L.P1;
+        }
+#endif
     }
+#if HVP_CENT_EVENT
+    L.sb = L.on && a >= 1 && i == I.n - 1 && I.xb2;
+    L.sbd = L.sb ? L.P1 - I.xb2[a + 1] - C.d_safe : 0.0;  // p_b2 <= p_b1 - d_safe + s_b2 (:284-291)
+#endif
     // ---- Hessian row t: closed-form block tridiagonal part
     const Forms F = forms(C, I, i);
     double* Hrow = S_lds.J + (L.on ? t : 0) * LD;
@@ -505,6 +575,13 @@ __device__ inline void most_violated(const Lane& L, const Consts& C, double y, d
             const bool sw = sat & 1u;
             consider(8, sw ? (b0 + 8) | REV : b0 + 8, sw ? -gap : gap, L.sf == 1 ? 2.0 * nn : nn, sc);
         }
+#if HVP_CENT_EVENT
+        if (L.sb) {
+            const double gap = L.sbd - L.P1 + p;  // p - p_b2 - d_safe
+            const bool sw = sat & 2u;
+            consider(9, sw ? (b0 + 9) | REV : b0 + 9, sw ? -gap : gap, nn, sc);
+        }
+#endif
     }
     if (id >= 0) score = best_v2 / best_nn;
 }
@@ -588,7 +665,7 @@ __device__ inline int solve(Lane& L, const Lds& Sg, const Consts& C, const Inst&
     int iter = 0, scans = 0;
     for (;;) {
         if (cut < 1e300 && (++scans & 3) == 0) {
-            const double lb = direct_cost(L, C, I, 0, Ki, nullptr, (int)(sat & 1u));
+            const double lb = direct_cost(L, C, I, 0, Ki, nullptr, (int)(sat & kSatMask));
             if (lb > cut) {
                 iters = iter;
                 *bound = lb;
@@ -614,7 +691,7 @@ __device__ inline int solve(Lane& L, const Lds& Sg, const Consts& C, const Inst&
         const int base = pr & (REV - 1);
         const bool rev = (pr & REV) != 0;
         const int owner = base / ROWS, rr = base % ROWS;
-        const bool psoft = rr == 8;
+        const bool psoft = soft_row(rr);
         // row normal as up to two segments of lanes: c = cf1 on [s1, s1 + n1), cf2 on [s2, s2 + n2)
         int s1 = owner, n1 = 1, s2 = owner - 1, n2 = 0;
         double cf1 = 0.0, cf2 = 0.0, dloc = 0.0;
@@ -645,7 +722,17 @@ __device__ inline int solve(Lane& L, const Lds& Sg, const Consts& C, const Inst&
                 cf1 = flip * sgn * L.ts;
                 n2 = 0;
                 if (t == owner) dloc = rr == 6 ? L.P1 - L.pmin : L.pmax - L.P1;
-            } else {
+            }
+#if HVP_CENT_EVENT
+            else if (rr == 9) {
+                s1 = owner - oa;
+                n1 = oa;
+                cf1 = -flip * L.ts;
+                n2 = 0;
+                if (t == owner) dloc = L.sbd;
+            }
+#endif
+            else {
                 s1 = owner - oa;
                 n1 = oa;
                 cf1 = flip * L.ts;
@@ -705,7 +792,7 @@ __device__ inline int solve(Lane& L, const Lds& Sg, const Consts& C, const Inst&
             const double t1 = k1key;
             double k3key = 1e300;
             int k3 = t;
-            if (t < nact && id >= 0 && (id & (REV - 1)) % ROWS == 8 && r < -1e-13 * rmax)
+            if (t < nact && id >= 0 && soft_row((id & (REV - 1)) % ROWS) && r < -1e-13 * rmax)
                 k3key = fmax(wgt - u, 0.0) / (-r);
             wargmin(k3key, k3);
             double t3 = k3key;
@@ -772,7 +859,7 @@ __device__ inline int solve(Lane& L, const Lds& Sg, const Consts& C, const Inst&
             const bool by_sat = t3 <= t1;
             if (by_sat) {
                 if (new_sat) {
-                    if (t == owner) sat ^= 1u;
+                    if (t == owner) sat ^= sat_bit(rr);
                     wsync();
                     pf.mark(8);
                     break;
@@ -786,7 +873,7 @@ __device__ inline int solve(Lane& L, const Lds& Sg, const Consts& C, const Inst&
                 const int ob = (dropped & (REV - 1)) / ROWS, brr = (dropped & (REV - 1)) % ROWS;
                 if (t == ob) {
                     act &= ~(1u << brr);
-                    if (by_sat) sat ^= 1u;
+                    if (by_sat) sat ^= sat_bit(brr);
                 }
             }
             const double u_n = __shfl_down(u, 1, W);
@@ -823,7 +910,7 @@ __device__ inline int solve(Lane& L, const Lds& Sg, const Consts& C, const Inst&
     int bad = 0;
     if (t < nact) {
         if (u < -1e-9 * wgt) bad = 1;
-        if ((id & (REV - 1)) % ROWS == 8 && u > wgt * (1.0 + 1e-9)) bad = 1;
+        if (soft_row((id & (REV - 1)) % ROWS) && u > wgt * (1.0 + 1e-9)) bad = 1;
     }
     return wor(bad) ? GI_FAIL_VERIFY : GI_OK;
 }
@@ -865,6 +952,18 @@ __device__ inline double direct_cost(const Lane& L, const Consts& C, const Inst&
         } else if (I.lsp && I.L == 0) {
             Jt += pen(k, p - I.xl[k] + C.d_safe);
         }
+#if HVP_CENT_EVENT
+        if (L.i == 0 && I.xf2) {
+            Jt += quad(p + C.t0 * v + C.d0 - I.xf2[k], v - I.xf2[N + 1 + k]);
+            Jt += pen(k, p - I.xf2[k] + C.d_safe);
+        }
+        if (L.i == I.n - 1 && I.xb2) {
+            const double pb = I.xb2[k], vb = I.xb2[N + 1 + k];
+            Jt += quad(pb + C.t0 * vb + C.d0 - p, vb - v);
+            const double g = pb - p + C.d_safe;  // row 9 (bit 1 of dual_sat)
+            Jt += (dual_sat < 0 || k < 2) ? C.w * fmax(0.0, g) : ((dual_sat & 2) ? C.w * g : 0.0);
+        }
+#endif
         return Jt;
     };
     double Jt = 0.0, u = 0.0;
@@ -880,5 +979,8 @@ __device__ inline double direct_cost(const Lane& L, const Consts& C, const Inst&
     return wsum(Jt);
 }
 
+#if HVP_CENT_EVENT
+}  // namespace ev
+#endif
 }  // namespace cent
 }  // namespace hvp

@@ -28,6 +28,9 @@
 
 namespace hvp {
 namespace cent {
+#if HVP_CENT_EVENT
+inline namespace ev {
+#endif
 
 constexpr int kTie = 64;  // near-optimal leaves kept for the tie rule (per search / task; <= W: lane j holds cost j)
 constexpr int kTieG = 64; // near-optimal leaves kept per platoon across the tasks of a split search
@@ -603,5 +606,8 @@ __device__ inline void bnb_platoon(Lane& L, const Lds& S, const Consts& C, const
     pf.flush();
 }
 
+#if HVP_CENT_EVENT
+}  // namespace ev
+#endif
 }  // namespace cent
 }  // namespace hvp

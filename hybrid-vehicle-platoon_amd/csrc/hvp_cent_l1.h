@@ -26,6 +26,9 @@
 
 namespace hvp {
 namespace cent {
+#if HVP_CENT_EVENT
+inline namespace ev {
+#endif
 
 constexpr int kLpHard = 8;   // V lo/hi, U lo/hi, A lo/hi, P lo/hi
 constexpr int kLpPair = 7;   // leader p, v; chain p, v; u; du; safe hinge
@@ -597,5 +600,8 @@ __device__ inline double lp_direct_cost(const Lane& L, const Consts& C, const In
     return wsum(Jt);
 }
 
+#if HVP_CENT_EVENT
+}  // namespace ev
+#endif
 }  // namespace cent
 }  // namespace hvp

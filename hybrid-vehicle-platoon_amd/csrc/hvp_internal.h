@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "hvp.h"
 #include "hvp_ipm.h"
@@ -155,4 +156,9 @@ struct hvp_handle {
     int nrec_slots = 0;         // slots allocated (nrec_want, halved until it fits the free HBM)
     unsigned long long nrec_epoch = 0;
     bool nrec_enable = true;  // hvp_set_node_records
+    // event-based controller (hvp_event.hip): the device copy of the last batch's descriptors and
+    // the host values it holds (a call with the same descriptors uploads nothing)
+    int32_t* event_desc = nullptr;
+    size_t event_desc_cap = 0;  // entries (4 int32 each)
+    std::vector<int32_t> event_desc_host;
 };

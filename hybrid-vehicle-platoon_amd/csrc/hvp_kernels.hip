@@ -750,6 +750,7 @@ void hvp_destroy(hvp_handle* h) {
     if (h->nclaim) (void)hipFree(h->nclaim);
     if (h->d_consts) (void)hipFree(h->d_consts);
     if (h->gadmm_redo) (void)hipFree(h->gadmm_redo);
+    if (h->event_desc) (void)hipFree(h->event_desc);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->evq0) (void)hipEventDestroy(h->evq0);

@@ -147,6 +147,32 @@ EXPORTS_SEQ = {
 }
 
 
+class HvpEventDesc(ctypes.Structure):
+    """hvp_event_desc (include/hvp_event.h): one local problem of the event-based controller."""
+
+    _fields_ = [("m", ctypes.c_int32), ("has_f2", ctypes.c_int32), ("has_b2", ctypes.c_int32),
+                ("leader", ctypes.c_int32)]
+
+
+_DESCP = ctypes.POINTER(HvpEventDesc)
+
+# the extension header include/hvp_event.h (event-based controller), as EXPORTS_SEQ
+EXPORTS_EVENT = {
+    "hvp_event_params_stride": ([ctypes.c_int], ctypes.c_int),
+    "hvp_event_validate": ([ctypes.POINTER(HvpProblem), ctypes.c_int, _DESCP], ctypes.c_int),
+    "hvp_event_layout": ([ctypes.c_int, ctypes.c_int, _DESCP], ctypes.c_int),
+    "hvp_event_solve_batch": ([_P, ctypes.c_int, _DESCP, _P, _P, ctypes.c_int] + [_P] * 9, ctypes.c_int),
+    "hvp_event_evaluate_batch": ([_P, ctypes.c_int, _DESCP] + [_P] * 8, ctypes.c_int),
+    "hvp_event_gather": ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_P] * 12, ctypes.c_int),
+    "hvp_event_select": ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [_P] * 13, ctypes.c_int),
+    "hvp_event_shift": ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_P] * 6, ctypes.c_int),
+}
+
+
+def event_params_stride(N: int) -> int:
+    return 6 + 6 * (N + 1)
+
+
 class HvpError(RuntimeError):
     pass
 
@@ -175,7 +201,7 @@ def load():
         )
     _init_torch_runtime()
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (argt, rest) in {**EXPORTS, **EXPORTS_SEQ}.items():
+    for name, (argt, rest) in {**EXPORTS, **EXPORTS_SEQ, **EXPORTS_EVENT}.items():
         fn = getattr(lib, name)
         fn.argtypes = argt
         fn.restype = rest

@@ -175,6 +175,22 @@ class PwaFrictionVehicle(Vehicle):
         Bm = _col(0.0, 1.0 / mass)
         return self._assemble([s.copy() for s in S], T, [A_lo, A_hi], [Bm, Bm.copy()], [c_lo, c_hi])
 
+    def get_u_for_constant_vel(self, v: float, j: int) -> float:
+        """The input that keeps v constant in gear j by the PWA dynamics (models.py:334-368):
+        v_dot = 0 in the friction piece that holds v (first match, [0, 1e-4] buffer)."""
+        if j < 1 or j > 6:
+            raise ValueError(f"{j} is not a valid gear.")
+        j = j - 1
+        if v < self.v_min and j == 0:
+            warnings.warn(f"Velocity {v} is below min {self.v_min}, using first gear but result will be approximate.")
+        elif v > self.v_max and j == 5:
+            warnings.warn(f"Velocity {v} is above max {self.v_max}, using last gear but result will be approximate.")
+        elif v < self.vl[j] or v > self.vh[j]:
+            raise ValueError(f"Velocity {v} is not valid for gear {j + 1}")
+        i = self.find_region(_col(0.0, v), np.zeros((1, 1)))
+        s = self.system
+        return (1 / (self.b[j] * s["B"][i][1, 0])) * (-s["A"][i][1, 1] * v - s["c"][i][1, 0])
+
     def get_discrete_system(self, ts: float) -> dict:
         """Forward-Euler discretisation of every region (models.py:370-387)."""
         disc = dict(self.system)

@@ -1,6 +1,8 @@
 """The n x N x seed sweep of the decentralised controller (configs[4], the reference's
 n_sweep*.py loops over ``simulate(Sim_n_task_2(n, seed), save=True)``) as ONE job on the device;
-``--controller seq`` sweeps the sequential controller (fleet_seq_mld.py, hvp/seq.py) instead.
+``--controller seq`` sweeps the sequential controller (fleet_seq_mld.py, hvp/seq.py) and
+``--controller event --event-iters K`` the event-based one (fleet_event_based.py, hvp/event.py)
+instead.
 
 Every (n, N) point runs its seeds as one batch of platoons in closed loop on the GPU -- the
 neighbour predictions (hvp_decent_params_batch), the n local MIQPs of every platoon
@@ -23,8 +25,15 @@ hvp_seq_stage_params (the neighbour blocks from the vehicle-major prediction sto
 hvp_solve_batch of vehicle i of every platoon, writing its trajectories straight into slot i of
 that store; PlatoonEnv.step after the last stage.  Its files are ``seq_{sim.id}_seed_{s}.pkl``.
 
+The event-based controller runs ``event_iters`` iterations per step, each four launches over the
+S n agents of the batch -- hvp_event_gather (the agents' parameter blocks and guesses from the
+vehicle-major guess store), hvp_event_evaluate_batch, hvp_event_solve_batch, hvp_event_select
+(the winner rule, the guess update and the per-platoon ``active`` flag) -- with no host read; a
+platoon nobody improved is still gathered and solved, it just cannot win.  hvp_event_shift after
+the plant step.  Its files are ``event_{K}_{sim.id}_seed_{s}.pkl``.
+
     python -m hvp.sweep --out results/ [--n 5 10 15 20] [--N 5 10 15] [--seeds 100] [--ep-len 150]
-                        [--controller {decent,seq}] [--leader-index K]
+                        [--controller {decent,seq,event}] [--leader-index K] [--event-iters K]
 """
 
 from __future__ import annotations
@@ -61,20 +70,29 @@ def shard(points, n_seeds: int, rank: int, world: int):
 
 def run_point(n: int, N: int, seeds, ep_len: int = 150, device: int = 0, out_dir: str | None = None,
               velocity_estimator: str = "none", warm_incumbent: bool = True, controller: str = "decent",
-              leader_index: int | None = None, return_pred: bool = False) -> dict:
+              leader_index: int | None = None, return_pred: bool = False, event_iters: int = 3) -> dict:
     """Closed-loop episodes of the decentralised (or, controller="seq", the sequential) controller
     for `seeds` (one platoon each) at (n, N), all on the device.  Returns per-seed X (T+1, 2n),
     U (T, n), R (T,), violations (T,), node_counts (T,), the step times and status_counts (local
     problems per HVP_* status; anything but optimal raises); writes the reference's results files
     if out_dir.  leader_index (seq only): None is vehicle 0 under the plain sim id, an index K
     also names the files ``..._lead_K`` as n_sweep_3.py's Sim_n_task_2(n, seed, leader_index) does.
-    return_pred (seq only): also XPRED (T, n, S, 2, N+1), every vehicle's prediction of every step."""
-    if controller not in ("decent", "seq"):
-        raise ValueError(f"controller must be 'decent' or 'seq', got {controller!r}")
+    return_pred (seq only): also XPRED (T, n, S, 2, N+1), every vehicle's prediction of every step.
+    controller="event": ``event_iters`` iterations per step (leader_index as for seq, the files'
+    ``_lead_K`` id included); also returns WINNERS (T, event_iters, S): the winning agent of every
+    iteration, -1 where nobody won or the platoon had stopped."""
+    if controller not in ("decent", "seq", "event"):
+        raise ValueError(f"controller must be 'decent', 'seq' or 'event', got {controller!r}")
     if controller == "decent" and (leader_index is not None or return_pred):
         raise ValueError("leader_index and return_pred are parameters of the seq path")
+    if controller == "event" and return_pred:
+        raise ValueError("return_pred is a parameter of the seq path")
     if controller == "seq" and velocity_estimator != "none":
         raise ValueError("the sequential controller has no velocity estimator (it observes no states)")
+    if controller == "event" and velocity_estimator != "none":
+        raise ValueError("the event-based controller has no velocity estimator (it observes no states)")
+    if controller == "event" and (event_iters < 1 or n < 2):
+        raise ValueError("the event-based controller needs event_iters >= 1 and n >= 2")
     lead = 0 if leader_index is None else int(leader_index)
     if not 0 <= lead < n:
         raise ValueError(f"leader_index {lead} outside 0..{n - 1}")
@@ -93,16 +111,23 @@ def run_point(n: int, N: int, seeds, ep_len: int = 150, device: int = 0, out_dir
     if T + N + 1 > leader_x.shape[1]:  # Sim_n_task_2 builds the trajectory for its own ep_len (150)
         raise ValueError(f"ep_len {T} with N = {N} needs {T + N + 1} leader samples; the Sim_n_task_2 "
                          f"trajectory holds {leader_x.shape[1]} (ep_len <= {leader_x.shape[1] - N - 1})")
-    systems, masses = [], []
+    systems, masses, fleet = [], [], []
     for sim in sims:
         pl = Platoon(n, vehicle_type="pwa_gear", masses=sim.masses)
         vehicles = pl.get_vehicles()
+        fleet.append(vehicles)
         for i, d in enumerate(pl.get_vehicle_system_dicts(Params.ts)):
             systems.append(tables.system_from_dict(d, tables.gears_of(vehicles[i])))
         masses.append(sim.masses)
-    solver = BatchSolver(tables.problem(N, sims[0].spacing_policy), systems, device=device)
     B = S * n
-    solver.reserve(S if controller == "seq" else B)  # seq: one stage of S instances at a time
+    if controller == "event":
+        from .cent import cent_problem
+        from .event import EventSolver
+
+        solver = EventSolver(cent_problem(N, sims[0].spacing_policy), systems, device=device)
+    else:
+        solver = BatchSolver(tables.problem(N, sims[0].spacing_policy), systems, device=device)
+        solver.reserve(S if controller == "seq" else B)  # seq: one stage of S instances at a time
     lx = torch.from_numpy(np.ascontiguousarray(leader_x)).to(dev)
     x = torch.from_numpy(x_init).to(dev)
     env = DeviceEnv(solver, torch.tensor(masses, dtype=torch.float64, device=dev), leader_index=lead)
@@ -154,6 +179,48 @@ def run_point(n: int, N: int, seeds, ep_len: int = 150, device: int = 0, out_dir
             NODES[t] = store["nodes"].max(dim=0).values
             if return_pred:
                 XPRED[t] = xpred
+    elif controller == "event":
+        from .event import initial_guesses, platoon_desc, threshold
+
+        desc = platoon_desc(n, lead, S)  # host: instance b = p n + i
+        vsys = torch.arange(B, dtype=torch.int32, device=dev).view(S, n).contiguous()
+        # the guess store, vehicle-major as the seq path's prediction store
+        # its episode-start values (on_episode_start) are the host rule's, uploaded once per episode:
+        # the same numbers the host coordinator starts from, so the two agree bit for bit where two
+        # agents' decreases tie (hvp_event_shift(init=1) is the same rule on the device)
+        g0 = [initial_guesses(x_init[k], fleet[k], N, Params.ts, False) for k in range(S)]
+        xg = torch.from_numpy(np.ascontiguousarray(np.stack([g[0] for g in g0], axis=1))).to(dev)
+        ug = torch.from_numpy(np.ascontiguousarray(np.stack([g[1] for g in g0], axis=1))).to(dev)
+        sys3 = torch.empty((B, 3), dtype=torch.int32, device=dev)
+        params = torch.empty((B, solver.stride), dtype=torch.float64, device=dev)
+        x_guess = torch.empty((B, 3, 2, N + 1), dtype=torch.float64, device=dev)
+        u_guess = torch.empty((B, 3, N), dtype=torch.float64, device=dev)
+        ev = {"cost": torch.empty(B, dtype=torch.float64, device=dev),
+              "status": torch.empty(B, dtype=torch.int32, device=dev)}
+        sol = solver.alloc_outputs(B, dev)
+        active = torch.empty(S, dtype=torch.int32, device=dev)
+        WINNERS = torch.empty((T, event_iters, S), dtype=torch.int32, device=dev)
+        codes = torch.arange(len(_abi.STATUS_NAMES), dtype=torch.int32, device=dev)
+        counts = torch.zeros(len(_abi.STATUS_NAMES), dtype=torch.int64, device=dev)
+        nofeas = torch.zeros((), dtype=torch.int64, device=dev)
+
+        def control(t, win):  # event_iters x (gather, evaluate, solve, select); nothing leaves the device
+            active.fill_(1)
+            NODES[t] = 0
+            for it in range(event_iters):
+                solver.gather_device(n, lead, x, vsys, xg, ug, None, win, sys3, params, x_guess, u_guess)
+                solver.evaluate_device(desc, sys3, params, x_guess, u_guess, None, ev)
+                solver.solve_device(desc, sys3, params, 0, sol)
+                solver.select_device(n, ev, sol, xg, ug, None, active, WINNERS[t, it], threshold)
+                # the reference stops iterating once nobody wins: a stopped platoon's later solves
+                # are not part of its episode (statuses, node counts)
+                live = WINNERS[t, it - 1] >= 0 if it else torch.ones(S, dtype=torch.bool, device=dev)
+                lb = live.repeat_interleave(n)
+                counts.add_(((sol["status"].reshape(-1, 1) == codes) & lb[:, None]).sum(dim=0))
+                NODES[t] = torch.maximum(NODES[t], torch.where(live, sol["nodes"].view(S, n).max(dim=1).values,
+                                                               torch.zeros_like(NODES[t])))
+                nofeas.add_((WINNERS[t, it] == -2).sum())
+            u.copy_(ug[:, :, 0].t())
     else:
         t_sys = torch.arange(B, dtype=torch.int32, device=dev)
         out = solver.alloc_outputs(B, dev)
@@ -188,12 +255,16 @@ def run_point(n: int, N: int, seeds, ep_len: int = 150, device: int = 0, out_dir
         V[t] = st["viol"]
         U[t] = u
         X[t + 1] = x
+        if controller == "event":
+            solver.shift_device(n, xg, ug, None)
         torch.cuda.current_stream(dev).synchronize()  # this run's stream (run_points runs several at once)
         step_s[t] = time.perf_counter() - t0
-    if controller == "seq":
+    if controller in ("seq", "event"):
         status_counts = {_abi.STATUS_NAMES[k]: int(c) for k, c in enumerate(counts.cpu().tolist()) if c}
+        if controller == "event" and int(nofeas.item()):
+            raise RuntimeWarning("No feasible solution found for any event based agent.")
         if set(status_counts) - {_abi.STATUS_NAMES[_abi.OPTIMAL]}:
-            raise RuntimeError(f"sweep point n={n} N={N} (seq): local problems not optimal: {status_counts}")
+            raise RuntimeError(f"sweep point n={n} N={N} ({controller}): local problems not optimal: {status_counts}")
     else:
         if int(bad.item()):
             raise RuntimeError(f"sweep point n={n} N={N}: {int(bad.item())} local MIQPs not optimal")
@@ -204,7 +275,9 @@ def run_point(n: int, N: int, seeds, ep_len: int = 150, device: int = 0, out_dir
            "nodes": Nh, "leader_x": leader_x, "controller": controller, "status_counts": status_counts}
     if return_pred:
         res["XPRED"] = h(XPRED)
-    name = "seq" if controller == "seq" else f"decent_vest_{velocity_estimator}"
+    if controller == "event":
+        res["WINNERS"] = h(WINNERS)
+    name = {"seq": "seq", "event": f"event_{event_iters}"}.get(controller, f"decent_vest_{velocity_estimator}")
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         # the batch's step time is every seed's solve time (the reference records the slowest
@@ -219,7 +292,7 @@ def run_point(n: int, N: int, seeds, ep_len: int = 150, device: int = 0, out_dir
 
 
 def run_points(n: int, N: int, seeds, ep_len: int, device: int, out_dir, estimator: str, streams: int = 2,
-               controller: str = "decent", leader_index: int | None = None):
+               controller: str = "decent", leader_index: int | None = None, event_iters: int = 3):
     """run_point over `streams` blocks of the seeds at once, each block on its own host thread and
     HIP stream (the blocks are independent platoons; one block's kernels fill the GPU while the
     other's launches finish or synchronise).  Returns the per-block results and the wall time."""
@@ -227,6 +300,8 @@ def run_points(n: int, N: int, seeds, ep_len: int, device: int, out_dir, estimat
 
     seeds = list(seeds)
     kw = {"controller": controller, "leader_index": leader_index}
+    if controller == "event":
+        kw["event_iters"] = event_iters
     K = max(1, min(streams, len(seeds)))
     blocks = [seeds[len(seeds) * j // K:len(seeds) * (j + 1) // K] for j in range(K)]
     res, errs = [None] * K, []
@@ -261,10 +336,13 @@ def main(argv=None) -> None:
     ap.add_argument("--ep-len", type=int, default=150)
     ap.add_argument("--out", default=None, help="directory of the results files (none: summary only)")
     ap.add_argument("--estimator", default="none", choices=["none", "two_point", "sat"])
-    ap.add_argument("--controller", default="decent", choices=["decent", "seq"],
-                    help="decent: fleet_decent_mld.py; seq: the sequential controller of fleet_seq_mld.py")
+    ap.add_argument("--controller", default="decent", choices=["decent", "seq", "event"],
+                    help="decent: fleet_decent_mld.py; seq: the sequential controller of fleet_seq_mld.py; "
+                         "event: the event-based controller of fleet_event_based.py")
     ap.add_argument("--leader-index", type=int, default=None,
-                    help="seq only: the vehicle that tracks the leader trajectory (files get the _lead_K id)")
+                    help="seq / event: the vehicle that tracks the leader trajectory (files get the _lead_K id)")
+    ap.add_argument("--event-iters", type=int, default=3,
+                    help="event only: iterations per step (n_sweep.py: sim_event(..., event_iters=3))")
     ap.add_argument("--streams", type=int, default=1,
                     help="seed blocks run concurrently per point (host threads / streams); measured 68 s vs 70 s "
                          "for the full grid, so 1 by default")
@@ -286,7 +364,7 @@ def main(argv=None) -> None:
     summary = []
     for n, N, seeds in shard(points, args.seeds, rank, world):
         rs, wall = run_points(n, N, seeds, args.ep_len, local, args.out, args.estimator, args.streams,
-                              args.controller, args.leader_index)
+                              args.controller, args.leader_index, args.event_iters)
         status_counts: dict = {}
         for r in rs:
             for k, c in r["status_counts"].items():
