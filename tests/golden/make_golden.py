@@ -60,8 +60,10 @@ Files (numpy .npz, no pickles):
                       problem); "exp_unique" marks the instances whose LP optimum is a unique vertex
   l1batch_n10_N10.npz the benchmark's n = 10, N = 10 min_1_norm platoons (seeds 0..255), one vehicle
                       (seed % 10) each: oracle status, cost and sequence only (no params)
+  event_*.npz         joint optima (cent_* layout) whose contiguous blocks are the local problems of the
+                      event-based controller at long horizons (event_fixtures; tests/test_event_horizons.py)
 Run:  python tests/golden/make_golden.py [sweep | gear | admm | admm_l1 [n10] | admm_gear | gadmm | cent [n10 | l1] | configs admm|gadmm
-                                          | l1 | l1_rollout | l1_long | l1stall | l1batch
+                                          | l1 | l1_rollout | l1_long | l1stall | l1batch | event [file ...]
                                           | l1_horizons [N ...] | admm_horizons [N ...]]
 """
 
@@ -794,7 +796,98 @@ def cent_fixtures(big: bool = False):
             cent_save(name, N, jobs, [f.get() for f in futs], cfg, model)
 
 
+# event_* sets: (file, n, N, model, [(seed, leader_index), ...], wall-clock budget in seconds from the
+# start of the run; the n = 5, N = 11 set: 20 minutes over all its seeds).  Oracle time per platoon when the
+# sets were made (8 cores, all 22 solves in flight): N = 6 under 1 s; n = 3, N = 11 4-7 s; n = 3, N = 16
+# 24 / 43 / 31 / 14 s; n = 4 4-17 s (N = 8), 29 / 36 s (N = 12), 74 s (N = 16); n = 5 16 / 65 s (N = 8) and
+# 131 / 105 s (N = 11); the gear model 37 / 188 s.  Seeds known not to finish in 270 s are not listed
+# (n = 3, N = 16: 0, 5; n = 4, N = 12 and 16: 0; n = 4, N = 16: 2; n = 5, N = 8: 0); n = 3, N = 16 seeds
+# (4, leader 0) and (3, leader 1) finish in 161 / 132 s, n = 5, N = 11 seed 2 in 238 s, and are left
+# out to keep the batches of the GPU test at two dozen wavefronts.
+EVENT_SETS = (
+    ("event_n3_N6.npz", 3, 6, 0, [(1, 0), (2, 1), (3, 2)], 600),
+    ("event_n3_N11.npz", 3, 11, 0, [(1, 0), (3, 1), (2, 2)], 600),
+    ("event_n3_N16.npz", 3, 16, 0, [(1, 0), (3, 0), (1, 1), (2, 2)], 900),
+    ("event_n4_N8.npz", 4, 8, 0, [(1, 0), (3, 2), (2, 1)], 600),
+    ("event_n4_N12.npz", 4, 12, 0, [(1, 0), (3, 1)], 600),
+    ("event_n4_N16.npz", 4, 16, 0, [(1, 0)], 900),
+    ("event_n5_N8.npz", 5, 8, 0, [(1, 0), (2, 3)], 600),
+    ("event_n5_N11.npz", 5, 11, 0, [(1, 0), (3, 0)], 1200),
+    ("event_gear_n4_N4.npz", 4, 4, 1, [(0, 0), (1, 2)], 600),
+)
+
+
+def _edge_steps(systems, r, tol=1e-6):
+    """(vehicle, step) pairs of a joint optimum whose velocity sits on the friction edge alpha: the two
+    modes that meet there (regions 3 and 4 of the gear PWA model, the two friction regions of a gear)
+    share the gear, so their dynamics coincide at the edge and the sequences through either cost the
+    same; which one a solver of a SUB-problem returns is its tie rule, not the optimum.  (At every other
+    band edge the input gain changes with the gear: a step there is an active row, not a tie.)
+    Platoons with such a step are left out of the event_* sets."""
+    alpha = float(O.friction_pwa_system(800.0)["T"][0][0])  # the edge does not depend on the mass
+    return [(i, k) for i in range(len(systems)) for k in range(1, r.x.shape[2] - 1)
+            if abs(r.x[i, 1, k] - alpha) <= tol]
+
+
+def event_fixtures(only=()):
+    """Joint optima for the event-based controller's long-horizon checks (tests/test_event_horizons.py):
+    the local problem over vehicles [lo, lo + m) of a centralised optimum, every other vehicle held at
+    its optimal trajectory, is the local MIQP of include/hvp_event.h, so one joint optimum pins every
+    contiguous block with m = 1, 2, 3.  Centralised fixtures in the cent_* layout (cent_save) with
+    Cfg(d0 = 10, t0 = 3), per-vehicle masses RandomState(seed).uniform(700, 1000, 5)[:n] and the leader
+    window leader_window(N, p0 = x0[2 L] + 30, v = 20); event_gear_n4_N4.npz on the (gear,
+    friction-region) tables (model = 1).  A platoon that does not finish inside its set's budget, is not
+    optimal or has a step on a band edge (_edge_steps) is reported and left out."""
+    import time
+    from multiprocessing import Pool
+
+    cfg = O.Cfg(d0=10.0, t0=3.0)
+    sets = [s for s in EVENT_SETS if not only or s[0] in only]
+    t0 = time.time()
+    pool = Pool(min(8, os.cpu_count() or 1))
+    try:
+        pending = []
+        for name, n, N, model, platoons, _ in sets:
+            jobs = []
+            for seed, L in platoons:
+                x0 = O.env_initial_state(n, seed).astype(float)
+                masses = np.random.RandomState(seed).uniform(700, 1000, 5)[:n].tolist()
+                jobs.append((masses, model, cfg, N, x0, leader_window(N, p0=x0[2 * L] + 30.0, v=20.0), L, False))
+            pending.append((jobs, [pool.apply_async(_timed_cent_case, (j,)) for j in jobs]))
+        for (name, n, N, model, platoons, budget), (jobs, futs) in zip(sets, pending):
+            keep_jobs, keep_res = [], []
+            for (seed, L), job, f in zip(platoons, jobs, futs):
+                try:
+                    (r, gear), dt = f.get(timeout=max(1.0, t0 + budget - time.time()))
+                except Exception as e:  # multiprocessing.TimeoutError
+                    print(f"  {name}: seed {seed}, leader {L}: not finished inside {budget} s ({type(e).__name__})", flush=True)
+                    continue
+                systems = [O.gear_friction_mld_system(m) if model == 1 else O.gear_pwa_system(m) for m in job[0]]
+                edges = _edge_steps(systems, r) if r.status == 0 else []
+                print(f"  {name}: seed {seed}, leader {L}: status {r.status}, {r.n_qps} QPs, {dt:.0f} s"
+                      + (f", band-edge steps {edges}: left out" if edges else ""), flush=True)
+                if r.status == 0 and not edges:
+                    keep_jobs.append(job)
+                    keep_res.append((r, gear))
+            if keep_jobs:
+                cent_save(name, N, keep_jobs, keep_res, cfg, model)  # each set saved as it completes
+            else:
+                print(f"{name}: no platoon finished; nothing written", flush=True)
+    finally:
+        pool.terminate()
+
+
+def _timed_cent_case(job):
+    import time
+
+    t0 = time.time()
+    return _cent_case(job), time.time() - t0
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "event":
+        event_fixtures(set(sys.argv[2:]))
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "cent":
         cent_fixtures(big=sys.argv[2] if len(sys.argv) > 2 else False)  # n10 | l1
         return

@@ -14,7 +14,8 @@ def fixture_names() -> list[str]:
     """The decentralised local-MIQP fixtures (the ADMM and centralised ones have their own layouts,
     the min_1_norm ones are listed by :func:`l1_fixture_names`)."""
     return sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "*.npz"))
-                  if not os.path.basename(p).startswith(("admm_", "gadmm_", "cent_", "l1_", "l1stall_", "l1batch_")))
+                  if not os.path.basename(p).startswith(("admm_", "gadmm_", "cent_", "event_", "l1_", "l1stall_",
+                                                         "l1batch_")))
 
 
 def l1_fixture_names() -> list[str]:

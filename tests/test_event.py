@@ -645,6 +645,18 @@ def test_gpu_device_loop_matches_host_coordinator(gpu_available, n):
     """hvp.sweep.run_point(controller="event") against TrackingEventBasedCoordinator seed by seed
     (N = 3, event_iters = 3, ep_len = 6, 8 seeds): the same winner in every iteration, first
     controls equal to 1e-9, every local problem optimal.  n = 2 and 3: the clipped ends."""
+    _device_loop_case(n, None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,leader_index", [(5, 2), (4, 3)])
+def test_gpu_device_loop_leader_not_first(gpu_available, n, leader_index):
+    """The same comparison with the leader window on a vehicle other than 0 (gather's leader block
+    for agents leader_index - 1 .. + 1, the layout's leader slot): a middle vehicle and the last."""
+    _device_loop_case(n, leader_index)
+
+
+def _device_loop_case(n, leader_index):
     from types import SimpleNamespace
 
     from hvp import tables
@@ -654,9 +666,10 @@ def test_gpu_device_loop_matches_host_coordinator(gpu_available, n):
     from hvp.sweep import run_point
 
     N, K, T, seeds = 3, 3, 6, list(range(8))
+    lead = 0 if leader_index is None else leader_index
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        dev = run_point(n, N, seeds, ep_len=T, controller="event", event_iters=K)
+        dev = run_point(n, N, seeds, ep_len=T, controller="event", event_iters=K, leader_index=leader_index)
     assert set(dev["status_counts"]) == {"OPTIMAL"}
     solved = 0
     for k, seed in enumerate(seeds):
@@ -664,14 +677,14 @@ def test_gpu_device_loop_matches_host_coordinator(gpu_available, n):
         # states of the device episode: both sides then see the same numbers, so agents whose
         # decreases tie (two agents that find the same improvement of their shared vehicles) win
         # or lose alike; the plant itself is pinned in tests/test_envdev.py
-        sim = Sim_n_task_2(n, seed=seed, N=N)
+        sim = Sim_n_task_2(n, seed=seed, leader_index=leader_index, N=N)
         platoon = Platoon(n, vehicle_type="pwa_gear", masses=sim.masses)
         systems, vehicles = platoon.get_vehicle_system_dicts(Params.ts), platoon.get_vehicles()
         mpcs = [LocalMpc(N, systems[L["lo"]:L["lo"] + L["m"]], L["num_vehicles_in_front"], L["num_vehicles_behind"],
                          sim.spacing_policy, L["rel_leader_index"],
                          gears=[tables.gears_of(v) for v in vehicles[L["lo"]:L["lo"] + L["m"]]])
-                for L in local_layout(n, 0)]
-        agent = TrackingEventBasedCoordinator(mpcs, vehicles, T, N, dev["leader_x"], False, Params.ts, K, 0)
+                for L in local_layout(n, lead)]
+        agent = TrackingEventBasedCoordinator(mpcs, vehicles, T, N, dev["leader_x"], False, Params.ts, K, lead)
         X = dev["X"][:, k]
         agent.on_episode_start(SimpleNamespace(x=X[0].reshape(-1, 1)), 0, X[0])
         for t in range(T):
@@ -692,6 +705,19 @@ def test_gpu_shift_kernel_matches_host_rules(gpu_available, model):
     """hvp_event_shift against the numpy rules: the episode-start guesses (states exactly at
     ts = 1; the holding input to rounding, its formula is written on the discrete tables there) and
     the per-step shift exactly."""
+    _shift_case(model, 4, 3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,P", [(4, 70), (2, 3)])
+@pytest.mark.parametrize("model", ["pwa_gear", "pwa_friction"])
+def test_gpu_shift_kernel_two_blocks_and_n2(gpu_available, model, n, P):
+    """The same comparison over a second thread block (P n = 280 > 256 items) and at n = 2, the
+    episode-start form and the per-step form each."""
+    _shift_case(model, n, P)
+
+
+def _shift_case(model, n, P):
     import torch
 
     from hvp import tables
@@ -699,7 +725,7 @@ def test_gpu_shift_kernel_matches_host_rules(gpu_available, model):
     from hvp.event import EventSolver, initial_guesses, shift_guesses
     from hvp.models import Platoon
 
-    n, N, P = 4, 3, 3
+    N = 3
     dev = torch.device("cuda", 0)
     gears = model == "pwa_friction"
     fleets = [Platoon(n, vehicle_type=model, masses=[700.0 + 60 * i + 11 * p for i in range(n)]) for p in range(P)]
